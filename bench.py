@@ -50,7 +50,21 @@ cpu     : the oracle (oracle/oracle.c: the reference's goroutine tile loop
           this process (cmd/raytracer/main.go:46, BASELINE configs[0]
           "workers=host cores"), rank 0 at N=1 only.
 
+plain   : without --full a run sets up (contexts, scene, each slot's set-up
+          launch), warms up, times the K steps and prints the line's head
+          (metric, value, unit, ms_per_step, dtype, the launch plan, config).
+          --full adds every other leg above and below after the timed steps
+          (counting launch and rooflines, per-kernel events of c4/c5,
+          one_frame_in_flight, first_frame_ms, render_e2e, the CPU baselines,
+          the oracle check; at N > 1 the share and 1-rank checks) and their
+          keys; value and ms_per_step mean the same in both.
+outputs : --dump-outputs DIR writes the last timed step's images (what the
+          caller of the timed path receives for that frame) as DIR/linear.npy
+          (float3, float32) and DIR/rgba.npy (RGBA8 as float32); the same
+          arguments give the same scene, seeds and so the same files.
+
 usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c2_committed|c3|c4|c5] [--weak]
+                       [--full] [--dump-outputs DIR]
 Multi-GPU: python bench.py --gpus N starts the N rank processes itself
           (launch_ranks: one child per GPU, started before any GPU call, rank
           0's JSON line forwarded, non-zero exit if any rank fails), or
@@ -135,8 +149,16 @@ def parse():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--weak", action="store_true", help="c2/c3: frame W x (H*N) (per-GPU work fixed)")
     ap.add_argument("--strided", action="store_true", help="N > 1: deal tiles t %% N instead of by estimated work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg of the line after the timed steps: the counting launch and "
+                         "rooflines, per-kernel events (c4/c5), the same frames one at a time, the first frame, "
+                         "render_e2e, the CPU baselines and the oracle check (N = 1), the share and 1-rank checks "
+                         "(N > 1).  Without it: set-up, warm-up, the timed steps, the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's images as DIR/linear.npy and "
+                         "DIR/rgba.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip render_e2e")
     ap.add_argument("--cpu-threads", type=int, default=0, help="CPU baseline threads (default: the affinity count)")
     ap.add_argument("--frames-in-flight", type=int, default=0,
                     help="launches in flight per rank (own context, stream and buffers each)")
@@ -472,6 +494,35 @@ def busy_ms(spans):
     if cur_e is not None:
         tot += cur_e - cur_s
     return tot
+
+
+DUMP_MAX_BYTES = 60 * 1000 * 1000  # --dump-outputs: both arrays together (under 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(dirname, slot, f, W, H):
+    """--dump-outputs: frame f of slot's last launch (the last timed step), as
+    the caller of the timed path receives it: linear.npy (float3 image,
+    float32 as rendered, [H][W][3]) and rgba.npy (the RGBA8 image as float32,
+    [H][W][4]).  A frame too large for DUMP_MAX_BYTES (c5) is written as the
+    same seeded sample of its pixels in both ([n][3], [n][4], pixel order)."""
+    import numpy as np
+
+    lin_d, rgba_d = slot.image(f)
+    lin = lin_d.cpu().numpy().reshape(H * W, 3)
+    rgba = rgba_d.cpu().numpy().reshape(H * W, 4).astype(np.float32)
+    pixel_bytes = lin.itemsize * 3 + rgba.itemsize * 4
+    n = min(W * H, DUMP_MAX_BYTES // pixel_bytes)
+    if n < W * H:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(W * H, size=n, replace=False))
+        lin, rgba = lin[idx], rgba[idx]
+    else:
+        lin, rgba = lin.reshape(H, W, 3), rgba.reshape(H, W, 4)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "linear.npy"), np.ascontiguousarray(lin, dtype=np.float32))
+    np.save(os.path.join(dirname, "rgba.npy"), np.ascontiguousarray(rgba))
+    return {"dir": dirname, "files": ["linear.npy", "rgba.npy"], "pixels": int(n), "of_pixels": W * H,
+            "sample_seed": DUMP_SAMPLE_SEED if n < W * H else None}
 
 
 def time_steps(slots, torch, dist, world, sts, warmup, comm, gstream, B):
@@ -963,14 +1014,73 @@ def main():
             sl.gather(torch, comm, gstream)
         slots.append(sl)
     barrier_sync(torch, dist, world, "set-up barrier", step="set-up", partition=PART_INFO)
-    with WD.guard("counting launch", step="counts", partition=PART_INFO):
-        counts = slots[0].counts(sts[0])  # algorithmic work of this rank's launch (counting variant, untimed)
-    barrier_sync(torch, dist, world, "counting barrier", step="counts", partition=PART_INFO)
-    prof_ctx = slots[0].ctx if cfg in WAVEFRONT else None
+    counts = None
+    if args.full:
+        with WD.guard("counting launch", step="counts", partition=PART_INFO):
+            counts = slots[0].counts(sts[0])  # algorithmic work of this rank's launch (counting variant, untimed)
+        barrier_sync(torch, dist, world, "counting barrier", step="counts", partition=PART_INFO)
+    prof_ctx = slots[0].ctx if cfg in WAVEFRONT and args.full else None
     if prof_ctx is not None:
         prof_ctx.profile(True)  # per-kernel HIP events in the timed frames (F = 1: every frame on slot 0)
     elapsed, kms, busy_frame_ms = time_steps(slots, torch, dist, world, sts, args.warmup, comm, gstream, B)
     plan = launches(sts, B)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step: the last frame of the last launch, copied now
+        # (--full's later timings reuse the slots)
+        dumped = dump_outputs(args.dump_outputs, slots[(len(plan) - 1) % len(slots)], len(plan[-1]) - 1, W, H)
+
+    def finish():
+        for sl in slots:
+            sl.close()
+        if comm is not None:
+            comm.close()
+        if world > 1:
+            with WD.guard("final barrier", step="exit", partition=PART_INFO):
+                dist.barrier()
+            dist.destroy_process_group()
+
+    rays = W * H * args.spp  # the whole frame (all ranks together)
+    value = rays * steps / elapsed / 1e6
+    workload = "%s %dx%d %dspp depth %d" % (label, W, H, args.spp, args.depth)
+    parallelism = "1 GPU" if world == 1 else "%d ranks: tiles %s, one %s gather per frame" % (
+        world, part_kind, "HOST (gloo, test mode: not a bench line)" if args.host_gather else "RCCL")
+    head = {
+        "metric": "Mrays/sec at 800x600x100spp max_depth=50 (sphere_reflections_light)" if cfg == "c2"
+        else "Mrays/sec (%s)" % cfg,
+        "value": round(value, 3),
+        "unit": "Mrays/s",
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / steps * 1e3, 4),
+        "full": args.full,
+        "dumped_outputs": dumped,
+        "frames_in_flight": F * B,
+        "launches_in_flight": F,
+        "frames_per_launch": B,
+        "launch_frames": [len(b) for b in plan],
+        "higher_is_better": True,
+        "scaling": "weak" if weak else "strong",
+        "vs_baseline": None,  # BASELINE.md has no published number on this hardware/config
+        "dtype": "f64",
+        "data": "synthetic: the reference's scene JSON%s, seeded counter-keyed RNG (seed %d + step: every "
+                "step a different image)" % (" (camera facing the objects)" if "facing" in spec else "",
+                                             args.seed),
+        "config": {
+            "workload": workload + ", soft shadows, recursive reflections",
+            "width": W, "height": H, "spp": args.spp, "max_depth": args.depth,
+            "parallelism": parallelism,
+            "frames_in_flight": F * B,
+            "frames_per_launch": B,
+        },
+    }
+    if not args.full:
+        # the plain run: nothing beyond the headline's own timed steps
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        finish()
+        return
     check_frame = None
     if world == 1:
         # the frame the oracle checks (check_equals_oracle): one from the last
@@ -997,7 +1107,7 @@ def main():
                                         args.strided or cfg in WAVEFRONT)
     check = share_sums = gathered_ok = None
     if world > 1 and not args.no_check:
-        # After the timed region, always at N > 1: the last timed frame (slot 0
+        # After the timed region, at N > 1 (--full): the last timed frame (slot 0
         # rendered it last, one frame per launch) proves its own image.  Every
         # rank hashes its packed share; rank 0 hashes each rank's slot of the
         # gather buffer the RCCL group filled (the transport check), then
@@ -1032,8 +1142,6 @@ def main():
     if world == 1 and not args.no_e2e and cfg in ("c2", "c2_committed", "c3"):
         e2e = render_e2e(rtgo, scene, W, H, args, local)
 
-    rays = W * H * args.spp  # the whole frame (all ranks together)
-    value = rays * steps / elapsed / 1e6
     kernel1_s = sum(kms1) / len(kms1) / 1e3  # this rank's average launch, one frame at a time
     kernelF_s = sum(kms) / len(kms) / 1e3     # ... with F frames in flight
     rank_kernel_ms = [kernel1_s * 1e3]
@@ -1047,7 +1155,6 @@ def main():
     # algorithmic HBM bytes: framebuffer write (float3 + RGBA8 = 16 B/pixel)
     # + the flattened scene read once per workgroup-resident copy (<= 4 KB)
     hbm_bytes = npix_local * 16 + 4096
-    workload = "%s %dx%d %dspp depth %d" % (label, W, H, args.spp, args.depth)
     if cfg in WAVEFRONT:
         # the soft-shadow stage (cone walks, the rays of
         # listed cones against their lists, the other soft rays through the
@@ -1112,42 +1219,15 @@ def main():
             check_oracle, check_info = oracle_check(check_frame, ref_img, W, H)
 
     if rank == 0:
-        parallelism = "1 GPU" if world == 1 else "%d ranks: tiles %s, one %s gather per frame" % (
-            world, part_kind, "HOST (gloo, test mode: not a bench line)" if args.host_gather else "RCCL")
         out = {
-            "metric": "Mrays/sec at 800x600x100spp max_depth=50 (sphere_reflections_light)" if cfg == "c2"
-            else "Mrays/sec (%s)" % cfg,
-            "value": round(value, 3),
-            "unit": "Mrays/s",
-            "n_gpus": world,
-            "steps": steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / steps * 1e3, 4),
+            **head,  # the plain run's line; the keys below are --full's
             "first_frame_ms": round(first_ms, 4) if first_ms is not None else None,
-            "frames_in_flight": F * B,
-            "launches_in_flight": F,
-            "frames_per_launch": B,
-            "launch_frames": [len(b) for b in plan],
             "one_frame_in_flight": {
                 "value": round(rays * steps / elapsed1 / 1e6, 3),
                 "ms_per_step": round(elapsed1 / steps * 1e3, 4),
                 "kernel_ms": round(kernel1_s * 1e3, 4),
             },
             "render_e2e": e2e,
-            "higher_is_better": True,
-            "scaling": "weak" if weak else "strong",
-            "vs_baseline": None,  # BASELINE.md has no published number on this hardware/config
-            "dtype": "f64",
-            "data": "synthetic: the reference's scene JSON%s, seeded counter-keyed RNG (seed %d + step: every "
-                    "step a different image)" % (" (camera facing the objects)" if "facing" in spec else "",
-                                                 args.seed),
-            "config": {
-                "workload": workload + ", soft shadows, recursive reflections",
-                "width": W, "height": H, "spp": args.spp, "max_depth": args.depth,
-                "parallelism": parallelism,
-                "frames_in_flight": F * B,
-                "frames_per_launch": B,
-            },
             "roofline": {
                 "bound": "valu",
                 "achieved": round(a64 + a32, 4),
@@ -1249,14 +1329,7 @@ def main():
                                 "cpu_baseline_linear_scan / gpu_over_cpu_linear_scan: the reference's linear "
                                 "hitWorld scan (renderer.go:333-346) on a 4-spp tile sample")
         print(json.dumps(out), flush=True)
-    for sl in slots:
-        sl.close()
-    if comm is not None:
-        comm.close()
-    if world > 1:
-        with WD.guard("final barrier", step="exit", partition=PART_INFO):
-            dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

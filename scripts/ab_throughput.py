@@ -2,8 +2,8 @@
 """A/B throughput of librtgo variants (dev tool, not the bench contract).
 
 usage: ab_throughput.py [--rounds R] [--config c2] [--steps K] LIB[@KEY=VAL,...] ...
-Each LIB runs `bench.py --config CFG --steps K --warmup 5 --no-cpu-baseline
---no-e2e` in its own process (RTGO_LIB=LIB), R rounds interleaved, and the
+Each LIB runs `bench.py --config CFG --steps K --warmup 5 --full
+--no-cpu-baseline --no-e2e` in its own process (RTGO_LIB=LIB), R rounds interleaved, and the
 line's value, ms_per_step, one-frame kernel ms and oracle check are printed
 per run and as medians per variant.  Experiment variants that change the
 image (timing bounds) show check_equals_oracle false.
@@ -34,7 +34,7 @@ def main():
                 k, _, v = kv.partition("=")
                 env[k] = v
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", args.config, "--steps", str(args.steps),
-                   "--warmup", "5", "--no-cpu-baseline", "--no-e2e"]
+                   "--warmup", "5", "--full", "--no-cpu-baseline", "--no-e2e"]
             p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
             line = next((json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")), None)
             if line is None:

@@ -4,7 +4,7 @@
 
 usage: batched_trace.py TRACE_DIR BENCH_JSON OUT.json
 
-bench.py (N = 1, c2/c3) issues, in order, per context: its set-up launch,
+bench.py --full (N = 1, c2/c3) issues, in order, per context: its set-up launch,
 the counting launch (render_kernel<true, ...>), the warm-up launches, the
 timed launches (their frame counts are the line's `launch_frames`), then the
 one-frame timing.  The timed launches are therefore the dominant kernel's

@@ -8,7 +8,7 @@ O=gpurun_out/k20_tuning.jsonl
 : > $O
 run() {
   local tag="$1"; shift
-  timeout -k 10 120 python3 bench.py --gpus 1 --steps 20 --warmup 5 ${K20_EXTRA:-} --no-cpu-baseline --no-e2e "$@" \
+  timeout -k 10 120 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 ${K20_EXTRA:-} --no-cpu-baseline --no-e2e "$@" \
     > gpurun_out/k20_tmp.log 2>&1 || return $?
   python3 -c "
 import json

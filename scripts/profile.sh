@@ -13,10 +13,11 @@ O=gpurun_out/profiles_${R}
 mkdir -p $O
 has() { case " $PARTS " in *" $1 "*) return 0 ;; esac; return 1; }
 if has driver; then
-  # the driver's own command, unmodified: its timed launches (batched frames,
+  # the driver's own command plus --full (the counting launch and roofline
+  # keys batched_trace.py reads; the same timed launches): they (batched frames,
   # launches in flight) are the ones the line's value and roofline describe
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${R}_driver -o run --output-format csv \
-    -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${R}_driver_bench_under_rocprof.json
+    -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${R}_driver_bench_under_rocprof.json
   cp "$(find gpurun_out/prof_${R}_driver -name '*kernel_stats.csv' | head -1)" $O/${R}_driver_kernel_stats.csv
   python3 scripts/batched_trace.py gpurun_out/prof_${R}_driver $O/${R}_driver_bench_under_rocprof.json \
     $O/${R}_driver_batched_trace.json
@@ -25,13 +26,13 @@ if has onefr; then
   # one frame per launch, one launch in flight: the launches whose HIP-event
   # time the roofline's kernel_ms uses
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${R}_trace -o run --output-format csv \
-    -- python3 bench.py --no-cpu-baseline --no-e2e --frames-per-launch 1 --frames-in-flight 1 \
+    -- python3 bench.py --full --no-cpu-baseline --no-e2e --frames-per-launch 1 --frames-in-flight 1 \
     > $O/${R}_bench_under_rocprof.json
   cp "$(find gpurun_out/prof_${R}_trace -name '*kernel_stats.csv' | head -1)" $O/${R}_kernel_stats.csv
 fi
 if has c4; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${R}_c4trace -o run --output-format csv \
-    -- python3 bench.py --config c4 --steps 2 --no-cpu-baseline > $O/${R}_c4_bench_under_rocprof.json
+    -- python3 bench.py --full --config c4 --steps 2 --no-cpu-baseline > $O/${R}_c4_bench_under_rocprof.json
   cp "$(find gpurun_out/prof_${R}_c4trace -name '*kernel_stats.csv' | head -1)" $O/${R}_c4_kernel_stats.csv
 fi
 if has pmc; then

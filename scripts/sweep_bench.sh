@@ -12,7 +12,7 @@ O=gpurun_out/sweep_$TAG.txt
 : > "$O"
 for spec in "$@"; do
   label=${spec%%|*}
-  args=${spec#*|}
+  args="--full ${spec#*|}"  # (--full: the line's one_frame_in_flight leg)
   timeout -k 10 120 python3 bench.py --no-cpu-baseline --no-e2e $args > gpurun_out/sweep_${TAG}_$label.json \
     2> gpurun_out/sweep_${TAG}_$label.err
   rc=$?
