@@ -189,6 +189,16 @@ struct rt_context {
   size_t tail_bytes = 0;
   int32_t tail_cap = 0, tail_spp = -1;
   uint32_t tail_epoch = 0;
+  // streamed launches: the schedule's live-pixel list
+  // (nlive x 4 ints, then live_pos per local pixel; nlive < 0: this schedule
+  // has none), cached with the blocks; the per-sample rows and the queue
+  // cursor (rows_cap bytes of rows, then the cursor word), allocated lazily
+  char* d_live = nullptr;
+  size_t live_cap = 0;
+  int32_t nlive = -1, live_local = 0;
+  char* d_rows = nullptr;
+  size_t rows_cap = 0;
+  int32_t wave_slots = 0;  // resident waves of render_stream_kernel on this device (its grid)
 };
 
 // Events for kernel classes [first, last] of one launch sequence: ev[k] opens
@@ -319,7 +329,8 @@ int rt_context_set_tuning(rt_context* c, const rt_tuning* t) {
       t->wf_paths < 0 || t->wf_chunk < 0 || t->wf_trav_block < 0 || t->wf_trav_block > 1024 || t->wf_trav_wgs < 0 ||
       t->wf_list_tries < 0 || t->wf_list_tries > 64 || t->tail_helpers < -1 || t->tail_helpers > 4096 ||
       t->tail_paths < 0 || t->tail_paths > 64 || t->tail_depth < 0 || t->tail_every < 0 || t->tail_every > 64 ||
-      t->tail_at < 0 || t->tail_at > 100) {
+      t->tail_at < 0 || t->tail_at > 100 || t->stream < -1 || t->stream > 1 || !(t->stream_max_mb >= 0) || t->stream_max_mb > 1e9 ||
+      t->stream_chunk < 0 || t->stream_chunk > 65536 || t->stream_order < 0 || t->stream_order > 1) {
     set_error("tuning value out of range");
     return RT_E_INVALID;
   }
@@ -451,7 +462,7 @@ void rt_context_destroy(rt_context* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_scene, (void*)c->d_counts, (void*)c->d_blocks, (void*)c->d_pilot, c->d_acc,
                   (void*)c->d_meas, (void*)c->d_split, (void*)c->d_sched, (void*)c->d_part, c->wf_mem, c->wf_rad,
-                  (void*)c->wf_ctl, (void*)c->d_tail})
+                  (void*)c->wf_ctl, (void*)c->d_tail, (void*)c->d_live, (void*)c->d_rows})
     dev_free(p);
   host_free(c->h_stage);
   host_free(c->h_small);
@@ -811,10 +822,26 @@ static double default_block_work(const rt_context* c, int frames = 1) {
 // primary-ray candidate masks apply (small linear-scan scenes)
 static bool masks_apply(const FlatScene& f) { return f.bvh.empty() && f.spheres.size() <= 64 && f.tris.size() <= 64; }
 
+// Could a render of these settings be streamed?  A staged
+// linear-scan scene, no sky, one sample pass, tail helpers off, no measured
+// schedule; `frames`: the frames per launch of the schedule's key.
+static bool stream_wanted(const rt_context* c, const KParams& p, const rt_settings* st, int frames) {
+  const rt_tuning& tn = c->tun;
+  // auto: launches of several frames of sphere-only scenes, where the A/B shows a
+  // gain (headline +22 %); with triangles it loses (C3 0.65x: the stream
+  // kernel's camera rays scan every primitive, the block kernel's visibility
+  // pass only the block's frustum candidates)
+  if (tn.stream == 0 || (tn.stream < 0 && (frames < 2 || !c->flat.tris.empty()))) return false;
+  return tn.stage && c->stage_bytes > 0 && c->flat.bvh.empty() && st->sky == RT_SKY_NONE && st->samples >= 1 &&
+         st->samples <= kMaxBlockSamples && p.spp_total == st->samples && tn.tail_helpers < 0 && !tn.measure;
+}
+
 static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream_t s, int frames = 1) {
   const FlatScene& f = c->flat;
   const int w = p->W, h = p->H, rank = p->rank, world = p->world;
   const rt_tuning& tn = c->tun;
+  // the live-pixel list of the streamed launches is built (and cached) with the blocks
+  const bool want_live = stream_wanted(c, *p, st, frames);
   int bigP = big_block_pixels(st->samples, tn);
   const double block_work = default_block_work(c, frames);
   const bool pilot = tn.pilot != 0;
@@ -826,7 +853,7 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
   const int64_t key[14] = {(int64_t)c->scene_gen, w, h, rank, world, st->samples, st->max_depth,
                            st->recursive_reflections, st->soft_shadows, bigP, (int64_t)(block_work * 16),
                            (pilot ? 1 + tn.pilot_depth : 0) | (int64_t)tn.split_samples << 16,
-                           (frustum ? 1 : 0) | (sky ? 2 : 0) | (tn.measure ? 4 : 0) | (int64_t)tn.split_depth << 8,
+                           (frustum ? 1 : 0) | (sky ? 2 : 0) | (tn.measure ? 4 : 0) | (want_live ? 8 : 0) | (int64_t)tn.split_depth << 8,
                            part ? (int64_t)c->part->id : 0};
   const bool masks = masks_apply(f);
   const bool new_key = memcmp(key, c->order_key, sizeof key) != 0;
@@ -841,6 +868,8 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
     c->num_blocks = 0;
     c->nsplit = 0;
     c->split_frames = 0;  // (the split rows are laid out again below)
+    c->nlive = -1;
+    c->live_local = local;
     c->masks_host.clear();
     c->d_masks = nullptr;
     if (local > 0) {
@@ -908,12 +937,19 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
         set_error(std::string("schedule launch failed: ") + hipGetErrorString((hipError_t)e));
         return fail_synced(RT_E_DEVICE);
       }
-      if (!hip_ok(hipMemcpyAsync(c->h_small, sp.totals, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s),
+      if (want_live) {  // live pixels per weight class and their number (totals[3])
+        e = sched_launch_live(sp, false, s);
+        if (e != hipSuccess) {
+          set_error(std::string("schedule launch failed: ") + hipGetErrorString((hipError_t)e));
+          return fail_synced(RT_E_DEVICE);
+        }
+      }
+      if (!hip_ok(hipMemcpyAsync(c->h_small, sp.totals, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s),
                   "schedule count read-back"))
         return fail_synced(RT_E_DEVICE);
       rc = wait_stream(c, s);  // (bounded under a renderer's deadline)
       if (rc) return rc;
-      memcpy(c->h_totals, c->h_small, 3 * sizeof(int32_t));
+      memcpy(c->h_totals, c->h_small, 4 * sizeof(int32_t));
       const int nblocks = c->h_totals[0], nsplit = c->h_totals[1];
       rc = grow(c, &c->d_blocks, &c->d_blocks_cap, (size_t)std::max(nblocks, 1) * kBlockInts * sizeof(int32_t));
       if (rc) return rc;
@@ -925,6 +961,19 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
       }
       c->num_blocks = nblocks;
       c->nsplit = nsplit;
+      if (want_live) {  // the list itself: nlive items, then every local pixel's position in it
+        const int nlive = std::max(0, std::min(c->h_totals[3], local * 1024));
+        rc = grow(c, &c->d_live, &c->live_cap, (size_t)std::max(nlive, 1) * 16 + (size_t)local * 1024 * sizeof(int32_t));
+        if (rc) return rc;
+        sp.live = (int32_t*)c->d_live;
+        sp.live_pos = (int32_t*)(c->d_live + (size_t)std::max(nlive, 1) * 16);
+        e = sched_launch_live(sp, true, s);
+        if (e != hipSuccess) {
+          set_error(std::string("schedule launch failed: ") + hipGetErrorString((hipError_t)e));
+          return RT_E_DEVICE;
+        }
+        c->nlive = nlive;
+      }
     }
     // (a rank with no tiles -- more ranks than the frame has tiles -- renders
     // nothing: no scheduler launch, no read-back of counts it never wrote)
@@ -1189,6 +1238,60 @@ static int render_wavefront(rt_context* c, const KParams& kp, const rt_settings*
   return RT_OK;
 }
 
+// A streamed launch of the nframes frames of p (its frame_*
+// entries; one frame: the single-frame fields), whose schedule holds a
+// live-pixel list: render_stream_kernel + resolve_rows_kernel per group of
+// consecutive frames whose rows (24 B per live pixel, sample and frame) fit
+// the budget rt_tuning.stream_max_mb (default 1 GiB: the headline launch's 25
+// frames take 573 MB).  *streamed stays false when the launch is not eligible
+// or not even two of its frames (the frame of a one-frame launch) fit: it then
+// takes the block kernel as before.
+static int render_stream(rt_context* c, const KParams& p, const rt_settings* st, int nframes, int key_frames,
+                         hipStream_t s, bool* streamed) {
+  *streamed = false;
+  if (!stream_wanted(c, p, st, key_frames) || c->nlive < 0 || p.counts || p.work_max || p.acc_mode != 0 || p.sky)
+    return RT_OK;
+  const rt_tuning& tn = c->tun;
+  const size_t budget = (size_t)((tn.stream_max_mb > 0 ? tn.stream_max_mb : 1024.0) * 1048576.0);
+  const size_t per_entries = (size_t)c->nlive * (size_t)p.spp, per_bytes = per_entries * 24;
+  size_t fit = (size_t)nframes;
+  if (per_entries > 0) fit = std::min(budget / per_bytes, (size_t)0x7FFFFFFF / per_entries);
+  const int group = (int)std::min<size_t>((size_t)nframes, fit);
+  if (group < std::min(nframes, 2)) return RT_OK;
+  if (c->wave_slots <= 0) c->wave_slots = stream_wave_slots(c->device);
+  if (c->wave_slots <= 0) {
+    set_error("stream launch: the device reports no compute units");
+    return RT_E_DEVICE;
+  }
+  // [cursor word, 256 B][rows of the largest group]
+  int rc = grow(c, &c->d_rows, &c->rows_cap, 256 + std::max<size_t>((size_t)group * per_bytes, 24));
+  if (rc) return rc;
+  StreamParams sp;
+  memset(&sp, 0, sizeof sp);
+  sp.live = (const int32_t*)c->d_live;
+  sp.live_pos = (const int32_t*)(c->d_live + (size_t)std::max(c->nlive, 1) * 16);
+  sp.tile_list = dev_tiles(c, p.W, p.H, p.rank, p.world);
+  sp.cursor = (unsigned int*)c->d_rows;
+  sp.rows = (double*)(c->d_rows + 256);
+  sp.nlive = c->nlive;
+  sp.npix = c->live_local * 1024;
+  sp.chunk = tn.stream_chunk > 0 ? tn.stream_chunk : 512;
+  sp.order = tn.stream_order;
+  for (int f0 = 0; f0 < nframes; f0 += group) {
+    sp.frame0 = f0;
+    sp.frames = std::min(group, nframes - f0);
+    sp.total = (uint32_t)((size_t)sp.frames * per_entries);
+    const int e = launch_stream(p, sp, c->wave_slots, s);
+    if (e != hipSuccess) {
+      set_error(std::string("stream launch failed: ") + hipGetErrorString((hipError_t)e));
+      return RT_E_DEVICE;
+    }
+    c->stats.stream_launches += 1;
+  }
+  *streamed = true;
+  return RT_OK;
+}
+
 // One frame (rt_context_render_async).  key_frames: the frames per launch
 // whose schedule this frame uses -- 1 for a frame of its own; n when it is
 // one of n frames that rt_context_render_frames_async renders one at a time
@@ -1278,11 +1381,16 @@ static int render_one(rt_context* c, int32_t w, int32_t h, const rt_settings* st
       rc = render_wavefront(c, p, st, s, counts != nullptr);
       if (rc) return rc;
     } else {
+      bool streamed = false;  // (rt_tuning.stream = 1: a one-frame launch through the stream path)
       if (npass == 1 && !counts) {
+        rc = render_stream(c, p, st, 1, key_frames, s, &streamed);
+        if (rc) return rc;
+      }
+      if (!streamed && npass == 1 && !counts) {
         rc = setup_tail(c, &p, s);
         if (rc) return rc;
       }
-      int e = launch_render(p, counts != nullptr, s);
+      int e = streamed ? (int)hipSuccess : launch_render(p, counts != nullptr, s);
       if (e != hipSuccess) {
         set_error(std::string("render launch failed: ") + hipGetErrorString((hipError_t)e));
         return RT_E_DEVICE;
@@ -1615,12 +1723,12 @@ int rt_context_render_frames_async(rt_context* c, int32_t w, int32_t h, const rt
   base_params(c, w, h, st, rank, world, layout, &p);
   hipStream_t s = (hipStream_t)stream;
   if (c->have_timing && s != c->last_stream) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
+  p.spp_total = st->samples;
   rc = prepare_schedule(c, &p, st, s, nframes);
   if (rc) return rc;
   // a new schedule key whose first frame is to measure (rt_tuning.measure):
   // that frame goes through the single-frame path, which records the paths
   if (c->tun.measure && c->meas_state == 1) return one_by_one();
-  p.spp_total = st->samples;
   p.nframes = nframes;
   for (int f = 0; f < nframes; ++f) {
     p.frame_key[f] = rt_rng_seed_key(seeds[f]);
@@ -1631,7 +1739,11 @@ int rt_context_render_frames_async(rt_context* c, int32_t w, int32_t h, const rt
   rc = setup_tail(c, &p, s);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(c->ev0, s));
-  const int e = launch_render(p, false, s);
+  // the streamed form where it applies, else the block kernel
+  bool streamed = false;
+  rc = render_stream(c, p, st, nframes, nframes, s, &streamed);
+  if (rc) return rc;
+  const int e = streamed ? (int)hipSuccess : launch_render(p, false, s);
   if (e != hipSuccess) {
     set_error(std::string("render launch failed: ") + hipGetErrorString((hipError_t)e));
     return RT_E_DEVICE;
@@ -1654,6 +1766,7 @@ int rt_context_get_stats(const rt_context* c, rt_context_stats* out) {
   out->blocks = c->num_blocks;
   out->split_pixels = c->nsplit;
   out->tail_exported = out->tail_errors = 0;
+  out->stream_live_pixels = c->nlive;
   if (c->d_tail) {
     rt_context* m = const_cast<rt_context*>(c);
     int rc = quiesce(m);

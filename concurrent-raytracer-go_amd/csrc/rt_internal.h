@@ -103,6 +103,11 @@ struct SchedParams {
   int32_t* cursor;             // per weight class: next record (pass 2)
   int32_t* totals;             // [0] blocks, [1] split pixels, [2] split-slot cursor
   int32_t* blocks;             // the records, heaviest class first (pass 2)
+  // the live-pixel list of the streamed launches (sched_launch_live)
+  int32_t* live_hist;          // per weight class: live pixels
+  int32_t* live_cursor;        // per weight class: next list position
+  int32_t* live;               // the list, heaviest class first, 4 ints each: {x, y, y * W + x (u32), lt * 1024 + pixel}
+  int32_t* live_pos;           // per local pixel: its list position, -1: not live
 };
 size_t sched_scratch_bytes(int local);
 void sched_layout(void* scratch, int local, SchedParams* p);
@@ -111,6 +116,11 @@ int sched_launch_pixels(const SchedParams& p, void* stream);
 // write = false: estimates, pass 1 (class counts, split count), scan;
 // write = true: pass 2 (the records)
 int sched_launch_blocks(const SchedParams& p, bool write, void* stream);
+// The live pixels of the rank's tiles (image pixels whose primary masks are
+// not empty; every image pixel without primary culling), after the estimates
+// of sched_launch_blocks(write = false).  write = false: counts per weight
+// class, scan, totals[3] = live pixels; write = true: live and live_pos.
+int sched_launch_live(const SchedParams& p, bool write, void* stream);
 
 // ---------------------------------------------------------------- kernels
 // PCG jump-ahead entries: cooperative soft shadows evaluate up to 64
@@ -264,6 +274,35 @@ struct KParams {
   int32_t tail_every_mask;  // the drain's iterations between export checks - 1 (a power of 2 - 1)
   int32_t tail_pos, _tpad2; // the helpers are workgroups [tail_pos, tail_pos + tail_helpers) of the grid
 };
+
+// ---- streamed launches: the samples of the live pixels of
+// `frames` frames form one queue of ENTRIES that a fixed set of persistent
+// one-wave workgroups drains (render_stream_kernel); each path's radiance
+// goes to its row, and resolve_rows_kernel sums a pixel's rows in sample
+// order and writes it.  Entry e -> (frame fl, live pixel i, sample s):
+//   order 0: e = (fl * nlive + i) * spp + s   (a chunk: neighbouring samples of one pixel)
+//   order 1: e = (i * spp + s) * frames + fl  (the frames interleaved)
+// Row of (fl, i, s): (fl * spp + s) * nlive + i, so the resolve's lanes (one
+// per live pixel) read consecutive rows.
+struct StreamParams {
+  const int32_t* live;         // SchedParams::live (4 ints per live pixel)
+  const int32_t* live_pos;     // SchedParams::live_pos
+  const int32_t* tile_list;    // per local tile: its global tile, or null: rank + lt * world
+  double* rows;                // [row][3] radiance
+  unsigned int* cursor;        // first entry not claimed yet (zeroed before the launch)
+  uint32_t total;              // entries: frames * nlive * spp (< 2^31)
+  int32_t nlive, npix;         // live pixels; local pixels (local tiles * 1024)
+  int32_t frame0, frames;      // the launch's frames [frame0, frame0 + frames) of KParams::frame_*
+  int32_t chunk, order;        // entries per claim; the entry order
+};
+struct StreamKArgs {           // the kernels' one argument: KParams at offset 0 (rt_kernel.hip fresh())
+  KParams k;
+  StreamParams s;
+};
+// render_stream_kernel on `wgs` one-wave workgroups (0: the device's resident
+// wave slots), then resolve_rows_kernel; the cursor is zeroed first.
+int launch_stream(const KParams& p, const StreamParams& sp, int wgs, void* stream);
+int stream_wave_slots(int device);
 
 // Enqueue the render kernel; returns hipError_t as int.
 int launch_render(const KParams& p, bool count, void* stream);

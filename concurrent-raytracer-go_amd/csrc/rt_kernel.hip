@@ -1364,13 +1364,30 @@ __device__ __forceinline__ void tail_helper(KArg karg, int* stack, double (*buf)
   }
 }
 
-template <bool kCount, bool kStage, bool kPilot, bool kSky, bool kTailT>
+// The stream kernel's part of its one argument (StreamKArgs: KParams first,
+// so fresh() serves it too), re-read where it is used like KParams.
+typedef const __attribute__((address_space(4))) StreamKArgs* SArg;
+__device__ __forceinline__ SArg sfresh() {
+  SArg k = (SArg)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+
+// kStream (render_stream_kernel): no blocks, no visibility
+// phase, no ring and no resolve -- the wave stages the scene once and then
+// takes entries (frame, live pixel, sample) off the launch-wide queue for as
+// long as there are any, with the SAME bounce code; a path's running L lives
+// in its lane's slot, and its final value goes to its row in global memory
+// (resolve_rows_kernel sums the rows).  The block-only LDS arrays shrink to
+// one element there.
+template <bool kCount, bool kStage, bool kPilot, bool kSky, bool kTailT, bool kStream = false>
 __device__ __forceinline__ void render_body(const KParams& pk) {
-  __shared__ uint32_t hbits[kMaxBlockSamples / 32];  // hit samples of the block
-  __shared__ int hoff[kMaxBlockSamples / 32 + 1];    // list offset of each bit word; [words] = #hits
-  __shared__ double slot[kRound][3];                 // radiance of the round's entries
-  __shared__ double psum[64][3];                     // per pixel: running sum over samples
-  __shared__ uint8_t lpix[64];                       // phase 1: the block's live pixels
+  static_assert(!kStream || (kStage && !kCount && !kPilot && !kSky && !kTailT), "the stream kernel is the staged product body");
+  __shared__ uint32_t hbits[kStream ? 1 : kMaxBlockSamples / 32];  // hit samples of the block
+  __shared__ int hoff[kStream ? 2 : kMaxBlockSamples / 32 + 1];    // list offset of each bit word; [words] = #hits
+  __shared__ double slot[kStream ? 64 : kRound][3];  // radiance of the round's entries (kStream: of each lane's path)
+  __shared__ double psum[kStream ? 1 : 64][3];       // per pixel: running sum over samples
+  __shared__ uint8_t lpix[kStream ? 1 : 64];         // phase 1: the block's live pixels
   __shared__ uint64_t skey[64];                      // per lane: its path's soft-shadow key (rt_soft_key, spec v4)
   // dynamic LDS (dyn_lds): [staged scene prefix (kStage)][BVH stack (stack_depth x 64 ints)]
   // tail helpers: render_kernel_tail exports a block's last
@@ -1400,11 +1417,11 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
     prow[lane] = -1;
     if (lane < kRound / 32) xm[lane] = 0u;
   }
-  const BlockLoc blk = block_loc(fresh(), block_of(fresh()));
+  const BlockLoc blk = kStream ? BlockLoc{} : block_loc(fresh(), block_of(fresh()));
   // a black block (up to 64 pixels x spp samples) sets no hit bits
   const int nwords = blk.black ? 0 : (blk.np * blk.ns + 31) >> 5;
   if (lane < nwords) hbits[lane] = 0;
-  {
+  if constexpr (!kStream) {
     // a later sample pass continues each pixel's running sum (acc_mode bit 0)
     double a0 = 0, a1 = 0, a2 = 0;
     if ((pk.acc_mode & 1) && blk.slot < 0 && lane < blk.np && blk.p0 + lane < 1024) {
@@ -1448,7 +1465,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
   const Cand all{~0ull, ~0ull};
 
   // ---- phase 1: visibility of the block's camera rays
-  {
+  if constexpr (!kStream) {
     // everything the loop needs is loaded once, before it (wave-uniform:
     // SGPRs); re-reading the kernarg segment inside the loop put scalar
     // load round trips on every iteration
@@ -1527,7 +1544,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
   }
   __syncthreads();
   // ---- the hit list: ascending sample ids (the <= 32 bit words scanned across the wave)
-  {
+  if constexpr (!kStream) {
     const int cw = lane < nwords ? __popc(hbits[lane]) : 0;
     int incl = cw;  // inclusive scan over the wave (Hillis-Steele)
     for (int off = 1; off < 64; off <<= 1) {
@@ -1538,7 +1555,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
     if (lane == 63) hoff[nwords] = incl;
   }
   __syncthreads();
-  const int nh = hoff[nwords];
+  const int nh = kStream ? 0 : hoff[nwords];
   // sample id (pixel * ns + sample - s0) of hit-list entry e < nh: the bit
   // word holding it (the last word whose list offset is <= e, by binary
   // search over hoff), then the (e - offset)-th set bit of that word.  No
@@ -1653,27 +1670,44 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
       }
     }
   };
-  if (nh > 0) {
+  if (kStream || nh > 0) {
     d3 o = mk(0, 0, 0), d = mk(0, 0, 0), T = mk(1, 1, 1);
     rt_rng rng{0};
-    int depth = 0, entry = 0;
+    int depth = 0, entry = 0;  // (kStream: `entry` is the path's row)
     bool alive = false;
     int next = 0, resolved = 0;  // wave-uniform: next entry to start; entries [0, resolved) summed
     int drain_it = 0;            // (tail helpers) iterations since every entry started
+    // (kStream) wave-uniform: the claimed entries not handed out yet, [qbeg,
+    // qend); dry: the launch's cursor is past the last entry
+    unsigned qbeg = 0, qend = 0;
+    bool dry = false;
     // The path's radiance L lives in its entry's ring slot (the slot is the
     // path's own until it finishes, and resolve_entries reads it only then):
     // read and written once per bounce, in VGPRs it held 6 registers through
     // the lighting section and pushed the loop into scratch spills
     // (scratch 40 -> 28 B/lane; headline 0.79 -> 0.775 ms).  Macros: the
     // same accessors as lambdas came out with 40 B/lane of scratch again.
-#define path_L() mk(slot[entry & (kRound - 1)][0], slot[entry & (kRound - 1)][1], slot[entry & (kRound - 1)][2])
+    // (kStream: the lane's own slot; a finished path's L goes to its row in
+    // global memory with plain stores, visible at the kernel's end)
+#define path_q() (kStream ? (int)threadIdx.x : entry & (kRound - 1))
+#define path_L() mk(slot[path_q()][0], slot[path_q()][1], slot[path_q()][2])
 #define set_path_L(v)                    \
   do {                                   \
     const d3 v_ = (v);                   \
-    const int q_ = entry & (kRound - 1); \
+    const int q_ = path_q();             \
     slot[q_][0] = v_.x;                  \
     slot[q_][1] = v_.y;                  \
     slot[q_][2] = v_.z;                  \
+  } while (0)
+#define stream_store_row()                                            \
+  do {                                                                \
+    if constexpr (kStream) {                                          \
+      double* r_ = sfresh()->s.rows + (size_t)(unsigned)entry * 3;    \
+      const int q_ = path_q();                                        \
+      r_[0] = slot[q_][0];                                            \
+      r_[1] = slot[q_][1];                                            \
+      r_[2] = slot[q_][2];                                            \
+    }                                                                 \
   } while (0)
     for (;;) {
       // (1) closest hit (hitWorld, renderer.go:170), in up to two passes: a
@@ -1693,8 +1727,67 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
       unsigned long long ts0 = 0;
 #endif
       for (int pass = 0;; ++pass) {
-        const unsigned long long freem = __ballot(!alive);
-        int limit = min(nh, resolved + kRound);
+        if constexpr (kStream) {
+          // Lanes without a path take the next entries of the launch-wide
+          // queue, in lane order.  The wave claims entries a chunk at a time
+          // (one relaxed add by one lane on the launch's cursor: a claim per
+          // entry would put ~0.9 M adds per headline frame on one address);
+          // when the claimed chunk runs out it claims the next one in the
+          // same pass (two rounds at most).  No wave ever waits for another.
+          unsigned long long fm = __ballot(!alive);
+          for (int r = 0; r < 2 && fm != 0; ++r) {
+            if (qbeg == qend) {
+              if (dry) break;
+              const SArg sk = sfresh();
+              unsigned v = 0;
+              if (lane_now() == 0)
+                v = __hip_atomic_fetch_add(sk->s.cursor, (unsigned)sk->s.chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              v = __builtin_amdgcn_readfirstlane(v);
+              // (the cursor stays below 2^32: total < 2^31, and every wave adds
+              // at most one chunk of <= 2^16 entries past the end)
+              qbeg = min(v, sk->s.total);
+              qend = min(v + (unsigned)sk->s.chunk, sk->s.total);
+              if (qbeg == qend) {
+                dry = true;
+                break;
+              }
+            }
+            const unsigned e = qbeg + (unsigned)lanes_below(fm);
+            if (!alive && e < qend) {
+              const SArg sk = sfresh();
+              const unsigned spp = (unsigned)sk->k.spp, nlive = (unsigned)sk->s.nlive;
+              unsigned fl, i, s;
+              if (sk->s.order == 0) {
+                const unsigned t = e / spp;
+                s = e - t * spp;
+                fl = t / nlive;
+                i = t - fl * nlive;
+              } else {
+                const unsigned nf = (unsigned)sk->s.frames, t = e / nf;
+                fl = e - t * nf;
+                i = t / spp;
+                s = t - i * spp;
+              }
+              const int4 it = reinterpret_cast<const int4*>(sk->s.live)[i];
+              const uint64_t fkey = sk->k.frame_key[sk->s.frame0 + (int)fl];
+              Counters nc;
+              // the camera ray and the soft-shadow key exactly as the block
+              // kernel's refill below builds them
+              camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, sk->k.aspect, sk->k.cam[0], sk->k.cam[1], sk->k.cam[2]),
+                                  it.x, it.y, (int)s, rng, o, d, nc);
+              skey[lane_now()] = rt_soft_key(fkey, (uint32_t)it.y * (uint32_t)sk->k.W + (uint32_t)it.x, (uint32_t)s);
+              entry = (int)((fl * spp + s) * nlive + i);
+              T = mk(1, 1, 1);
+              set_path_L(mk(0, 0, 0));
+              depth = 0;
+              alive = true;
+            }
+            qbeg = min(qend, qbeg + (unsigned)__popcll(fm));
+            fm = __ballot(!alive);
+          }
+        }
+        const unsigned long long freem = kStream ? 0ull : __ballot(!alive);
+        int limit = kStream ? 0 : min(nh, resolved + kRound);
         if (freem != 0 && next == limit && next < nh) {
           // the ring is full and lanes are idle: sum every entry before the
           // earliest one still running (a wave-wide min over the live lanes)
@@ -1727,7 +1820,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
         }
         // lanes without a path take the next entries, in lane order
         const int e = next + lanes_below(freem);
-        if (!alive && e < limit) {
+        if (!kStream && !alive && e < limit) {
           KArg k = fresh();
           const BlockLoc loc = block_loc(k, block_of(k));
           const int id = entry_id(e), ns = loc.ns;
@@ -1746,7 +1839,9 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
         next = min(limit, next + __popcll(freem));
         if (pass == 0) {
           if (__ballot(alive) == 0) {  // wave-uniform
-            outer = next >= nh ? 2 : 1;  // every entry done / ring full of finished entries: resolve, then refill
+            // every entry done / ring full of finished entries: resolve, then refill
+            // (kStream: no lane found an entry, so the queue is dry: the wave leaves)
+            outer = (kStream ? dry : next >= nh) ? 2 : 1;
             break;
           }
 #ifdef RT_WG_TIMING
@@ -1879,7 +1974,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               }
             }
           }
-          if constexpr (kStage && !kCount && !kPilot && RT_SOLO) {
+          if constexpr (kStage && !kCount && !kPilot && !kStream && RT_SOLO) {
             // one path left (no free lane found an entry to start): the whole
             // wave runs it to its end (solo_path)
             const unsigned long long am = __ballot(alive);
@@ -1942,6 +2037,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               atomicMax(k->work_max + px, (unsigned)depth + 1u);
               atomicAdd(k->work_sum + px, (unsigned)depth + 1u);
             }
+            stream_store_row();
             alive = false;  // finished: its radiance is in its slot, the lane is free for the second pass
           } else {
             shade = true;
@@ -1970,7 +2066,9 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           }
         }
         // a second pass when enough lanes are free and entries are left
-        if (pass > 0 || kRefill2Min <= 0 || __popcll(__ballot(!alive)) < kRefill2Min || next >= nh) break;
+        if (pass > 0 || kRefill2Min <= 0 || __popcll(__ballot(!alive)) < kRefill2Min ||
+            (kStream ? dry && qbeg == qend : next >= nh))
+          break;
       }  // passes
       if (outer == 1) continue;
       if (outer == 2) break;
@@ -2154,19 +2252,53 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           atomicMax(k->work_max + px, (unsigned)depth + 1u);
           atomicAdd(k->work_sum + px, (unsigned)depth + 1u);
         }
+        stream_store_row();
         alive = false;  // (its radiance is in its slot already)
       }
     }
-    __syncthreads();
-    resolve_entries(resolved, nh);
-    __syncthreads();
+    if constexpr (!kStream) {
+      __syncthreads();
+      resolve_entries(resolved, nh);
+      __syncthreads();
+    }
   }
 #undef path_L
 #undef set_path_L
+#undef path_q
+#undef stream_store_row
 #ifdef RT_WG_TIMING
   const unsigned long long t_loop = __builtin_amdgcn_s_memrealtime();
   if (dbg_bprev >= 0) dbg_bclk[dbg_bprev] += __builtin_amdgcn_s_memtime() - dbg_bts;
 #endif
+  if constexpr (kStream) {
+    // every row of this wave's paths is written; resolve_rows_kernel, the next
+    // kernel on the stream, sums them
+#ifdef RT_WG_TIMING
+    if (fresh()->dbg && threadIdx.x == 0) {  // the block kernel's record (below), without a block
+      unsigned long long* r = fresh()->dbg + (size_t)blockIdx.x * kDbgStride;
+      r[0] = t_start;
+      r[1] = t_loop;
+      r[2] = __builtin_amdgcn_s_memrealtime();
+      r[3] = dbg_hit;
+      r[4] = dbg_light;
+      r[5] = dbg_soft;
+      r[6] = dbg_vis;
+      r[7] = dbg_iter;
+      r[8] = dbg_hard;
+      r[9] = dbg_scat;
+      r[10] = dbg_alive;
+      r[11] = dbg_coop;
+      r[12] = dbg_seq;
+      r[13] = r[14] = 0;
+      for (int i = 0; i < 5; ++i) {
+        r[32 + i] = dbg_bclk[i];
+        r[37 + i] = dbg_bcnt[i];
+      }
+      r[42] = r[43] = 0;
+    }
+#endif
+    return;
+  }
 
   // ---- phase 3 (final): mean, tone map, one write per pixel
   KArg k = fresh();
@@ -2316,6 +2448,75 @@ __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_kernel(const KPa
 // the staged product render with tail helpers (rt_tuning.tail_helpers > 0)
 __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_kernel_tail(const KParams pk) {
   render_body<false, true, false, false, true>(pk);
+}
+
+// ---- streamed launches
+// One persistent one-wave workgroup per resident wave slot; each drains the
+// launch-wide entry queue (render_body<kStream>).
+__global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_stream_kernel(const StreamKArgs a) {
+  render_body<false, true, false, false, false, true>(a.k);
+}
+// After it on the same stream: one lane per pixel of the rank's tiles, per
+// frame of the launch (blockIdx.y).  Lane t writes local pixel t black when it
+// is not live (what the block kernel's epilogue writes for it: a sum of +0),
+// and sums live pixel t's spp rows in sample order from +0 -- tracePixel's sum
+// (renderer.go:150-163), a miss having stored +0 -- then mean, tone map and
+// write through store_pixel, as the block kernel's epilogue.  Consecutive
+// lanes read consecutive rows (StreamParams: row = (fl * spp + s) * nlive + i).
+__global__ __launch_bounds__(256) void resolve_rows_kernel(const StreamKArgs a) {
+  const KArg k = fresh();
+  const SArg sk = sfresh();
+  const unsigned t = blockIdx.x * 256u + threadIdx.x;
+  const int fl = (int)blockIdx.y, fr = sk->s.frame0 + fl;
+  if (t < (unsigned)sk->s.npix && sk->s.live_pos[t] < 0) {
+    const int lt = (int)(t >> 10), tp = (int)(t & 1023u);
+    const int tile = sk->s.tile_list ? sk->s.tile_list[lt] : k->rank + lt * k->world;
+    const int x = (tile % k->tiles_x) * 32 + (tp & 31), y = (tile / k->tiles_x) * 32 + (tp >> 5);
+    if (tile < k->ntiles && x < k->W && y < k->H)
+      store_pixel(k, fr, k->layout == RT_LAYOUT_IMAGE ? (size_t)y * k->W + x : (size_t)t, 0.0, 0.0, 0.0);
+  }
+  if (t < (unsigned)sk->s.nlive) {
+    const int4 it = reinterpret_cast<const int4*>(sk->s.live)[t];
+    const size_t nlive = (size_t)sk->s.nlive;
+    const int spp = k->spp;
+    const double* __restrict__ row = sk->s.rows + ((size_t)fl * spp * nlive + t) * 3;
+    double sx = 0, sy = 0, sz = 0;
+    for (int s = 0; s < spp; ++s, row += nlive * 3) {
+      sx += row[0];
+      sy += row[1];
+      sz += row[2];
+    }
+    store_pixel(k, fr, k->layout == RT_LAYOUT_IMAGE ? (size_t)(uint32_t)it.z : (size_t)it.w, sx, sy, sz);
+  }
+}
+
+int stream_wave_slots(int device) {
+  hipDeviceProp_t pr;
+  if (hipGetDeviceProperties(&pr, device) != hipSuccess || pr.multiProcessorCount <= 0) return 0;
+  return pr.multiProcessorCount * 4 * RT_WAVES_PER_SIMD;  // CUs x SIMDs x waves per SIMD of the kernel
+}
+
+int launch_stream(const KParams& pin, const StreamParams& sp, int wgs, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  StreamKArgs a;
+  a.k = pin;
+  a.s = sp;
+  KParams& p = a.k;
+  if (p.nframes <= 1) {  // one frame: entry 0 from the single-frame fields (as launch_render)
+    p.nframes = 1;
+    p.frame_key[0] = p.seed_key;
+    p.frame_lin[0] = p.out_linear;
+    p.frame_rgba[0] = p.out_rgba;
+  }
+  p.tail = nullptr;
+  if (p.stage_bytes <= 0 || p.use_bvh || wgs <= 0 || sp.frames <= 0 || sp.npix <= 0) return (int)hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(sp.cursor, 0, sizeof(unsigned int), st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(render_stream_kernel, dim3(wgs), dim3(64), render_shmem(p), st, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(resolve_rows_kernel, dim3((unsigned)((sp.npix + 255) / 256), (unsigned)sp.frames), dim3(256), 0, st, a);
+  return (int)hipGetLastError();
 }
 
 // Gathered shares [world][share_bytes] (each: [max_local][1024] float3, then

@@ -394,7 +394,84 @@ __global__ __launch_bounds__(64) void sched_tile_work(const SchedParams p, float
   if (lane == 0) out[lt] = (float)(a * (double)max(p.spp, 1));
 }
 
+// The live pixels of the rank's tiles, for the streamed launches (DESIGN.md
+// §4.7): image pixels whose own primary masks are not empty (every image
+// pixel when primary culling is off), listed heaviest estimate first so the
+// launch's long chains start early.  A counting sort by weight class (64
+// per unit of estimated work, 8 classes per octave): pass 1 (kWrite = false)
+// counts the classes, sched_live_scan turns the counts into cursors and
+// totals[3], pass 2 writes each pixel at its class's cursor.  Counts per
+// workgroup in LDS, one global atomic per class and workgroup.  The order
+// inside a class follows the atomics; the image does not depend on it.
+template <bool kWrite>
+__global__ __launch_bounds__(256) void sched_live(const SchedParams p) {
+  __shared__ int s_cnt[kBuckets], s_base[kBuckets];
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  for (int b = threadIdx.x; b < kBuckets; b += 256) s_cnt[b] = 0;
+  __syncthreads();
+  bool live = false;
+  int x = 0, y = 0, b = 0, r = 0;
+  if (i < (size_t)p.local * 1024) {
+    const int lt = (int)(i >> 10), q = (int)(i & 1023);
+    const int t = p.tile_list ? p.tile_list[lt] : p.rank + lt * p.world;
+    x = (t % p.tiles_x) * 32 + (q & 31);
+    y = (t / p.tiles_x) * 32 + (q >> 5);
+    live = t < p.ntiles && x < p.W && y < p.H &&
+           (!(p.frustum && p.tile_masks) || (p.pixmask[i * 2] | p.pixmask[i * 2 + 1]) != 0);
+    if (live) {
+      b = bucket_of((double)fabsf(p.est[i]) * 64.0);
+      r = atomicAdd(&s_cnt[b], 1);
+    }
+  }
+  __syncthreads();
+  if (!kWrite) {
+    for (int k = threadIdx.x; k < kBuckets; k += 256)
+      if (s_cnt[k]) atomicAdd(&p.live_hist[k], s_cnt[k]);
+    return;
+  }
+  for (int k = threadIdx.x; k < kBuckets; k += 256) s_base[k] = s_cnt[k] ? atomicAdd(&p.live_cursor[k], s_cnt[k]) : 0;
+  __syncthreads();
+  if (i < (size_t)p.local * 1024) {
+    int pos = -1;
+    if (live) {
+      pos = s_base[b] + r;
+      reinterpret_cast<int4*>(p.live)[pos] = make_int4(x, y, (int)((uint32_t)y * (uint32_t)p.W + (uint32_t)x), (int)i);
+    }
+    p.live_pos[i] = pos;
+  }
+}
+
+__global__ __launch_bounds__(kBuckets) void sched_live_scan(const SchedParams p) {
+  __shared__ int s[kBuckets];
+  const int i = threadIdx.x;
+  s[i] = p.live_hist[i];
+  __syncthreads();
+  for (int off = 1; off < kBuckets; off <<= 1) {
+    const int v = i >= off ? s[i - off] : 0;
+    __syncthreads();
+    s[i] += v;
+    __syncthreads();
+  }
+  p.live_cursor[i] = s[i] - p.live_hist[i];
+  if (i == kBuckets - 1) p.totals[3] = s[i];
+}
+
 }  // namespace
+
+int sched_launch_live(const SchedParams& p, bool write, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (p.local <= 0) return hipSuccess;
+  const unsigned n = (unsigned)(((size_t)p.local * 1024 + 255) / 256);
+  if (!write) {
+    const hipError_t e = hipMemsetAsync(p.live_hist, 0, kBuckets * sizeof(int32_t), s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((sched_live<false>), dim3(n), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(sched_live_scan, dim3(1), dim3(kBuckets), 0, s, p);
+  } else {
+    hipLaunchKernelGGL((sched_live<true>), dim3(n), dim3(256), 0, s, p);
+  }
+  return (int)hipGetLastError();
+}
 
 int sched_launch_tile_work(const SchedParams& p, float* tile_work, void* stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -406,9 +483,10 @@ int sched_launch_tile_work(const SchedParams& p, float* tile_work, void* stream)
 }
 
 size_t sched_scratch_bytes(int local) {
-  // pixmask (2 u64 / pixel) | est (f32 / pixel) | pilot blocks (16 / tile) | hist | cursor | totals
+  // pixmask (2 u64 / pixel) | est (f32 / pixel) | pilot blocks (16 / tile) | hist | cursor | totals (16 ints)
+  // | live hist | live cursor
   return (size_t)local * 1024 * 16 + (size_t)local * 1024 * 4 + (size_t)local * 16 * kBlockInts * 4 +
-         2 * kBuckets * 4 + 64;
+         2 * kBuckets * 4 + 64 + 2 * kBuckets * 4;
 }
 
 void sched_layout(void* scratch, int local, SchedParams* p) {
@@ -422,6 +500,8 @@ void sched_layout(void* scratch, int local, SchedParams* p) {
   p->hist = (int32_t*)m;
   p->cursor = p->hist + kBuckets;
   p->totals = p->cursor + kBuckets;
+  p->live_hist = p->totals + 16;
+  p->live_cursor = p->live_hist + kBuckets;
 }
 
 // (see preload_render_kernels)

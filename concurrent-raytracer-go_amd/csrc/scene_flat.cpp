@@ -306,6 +306,10 @@ void rt_tuning_default(rt_tuning* t) {
   // tail helpers: 64 at the end of the launch; drains
   // checked every 4th iteration, paths of >= 2 bounces, <= 4 left (the 0s)
   t->tail_helpers = -1;  // measured a net loss on the headline frame
+  // streamed launches: auto; the frames of a launch
+  // interleaved, 512 entries per claim (the 0) -- the measured best of the sweep
+  t->stream = -1;
+  t->stream_order = 1;
 }
 
 int32_t rt_num_tiles(int32_t w, int32_t h) {

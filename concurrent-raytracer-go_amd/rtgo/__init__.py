@@ -151,7 +151,11 @@ class Tuning(ctypes.Structure):
         ("tail_depth", ctypes.c_int32),
         ("tail_every", ctypes.c_int32),
         ("tail_at", ctypes.c_int32),
-        ("_tail_pad", ctypes.c_int32),
+        ("stream", ctypes.c_int32),
+        ("stream_chunk", ctypes.c_int32),
+        ("stream_max_mb", ctypes.c_double),
+        ("stream_order", ctypes.c_int32),
+        ("_stream_pad", ctypes.c_int32),
     ]
 
 
@@ -177,7 +181,7 @@ class ContextStats(ctypes.Structure):
 
     _fields_ = [(n, ctypes.c_int64) for n in ("schedules_built", "measuring_frames", "frames", "launches",
                                              "batched_launches", "blocks", "split_pixels", "tail_exported",
-                                             "tail_errors")]
+                                             "tail_errors", "stream_launches", "stream_live_pixels")]
 
 
 COUNT_FIELDS = [

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 5  /* 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 6  /* 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -345,7 +345,19 @@ typedef struct {
   int32_t tail_depth;     /* ... each at least this many bounces deep; 0: 2 */
   int32_t tail_every;     /* ... checked every this many iterations of the block's drain (rounded up to a power of 2, at most 64); 0: 4 */
   int32_t tail_at;        /* the helpers follow this percentage of the launch's main workgroups (1..100); 0: 100 */
-  int32_t _tail_pad;
+  /* streamed launches (megakernel, staged linear-scan scenes):
+   * the samples of the live pixels of a launch's frames form one queue that
+   * persistent waves drain; a resolve kernel sums each pixel's per-sample rows */
+  int32_t stream;         /* -1: auto (rt_tuning_default: launches of several frames, where it is measured to
+                             gain); 0: never; 1: whenever eligible, one-frame launches too */
+  int32_t stream_chunk;   /* queue entries a wave claims at a time (1..65536); 0: 512 */
+  double stream_max_mb;   /* row buffer budget in MiB, fractions allowed (24 B per live pixel, sample and
+                             frame); 0: 1024.  A launch whose rows exceed it runs as groups of consecutive
+                             frames; when not even two frames (one, of a one-frame launch) fit, the launch
+                             takes the block kernel */
+  int32_t stream_order;   /* entry order; 0: frame-major (a chunk holds neighbouring samples of one pixel),
+                             1: the launch's frames interleaved (rt_tuning_default: 1) */
+  int32_t _stream_pad;
 } rt_tuning;
 #define RT_PARTITION_AUTO 0
 #define RT_PARTITION_STRIDED 1
@@ -398,6 +410,10 @@ typedef struct {
    * context's tail buffers were laid out, and a helper error word (0: none);
    * reading them waits for the context's last render */
   int64_t tail_exported, tail_errors;
+  /* streamed launches (rt_tuning.stream): stream + resolve kernel pairs enqueued (a launch split under the
+   * row budget counts one per group of frames), and the live pixels of the schedule last used (-1: the
+   * schedule has no live-pixel list) */
+  int64_t stream_launches, stream_live_pixels;
 } rt_context_stats;
 int rt_context_get_stats(const rt_context* ctx, rt_context_stats* out);
 /* Debug (tail helpers), cumulative since the context's tail

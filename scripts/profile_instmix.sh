@@ -35,6 +35,13 @@ for scene in ${INSTMIX_SCENES:-headline c4}; do
     done
   else
     suf=$([ $FR = 1 ] && echo "" || echo "_b$FR")
+    # a batched launch of the headline streams by default: its
+    # kernel is the one to report, as *_headline_bB_stream.json
+    if [ $FR != 1 ]; then
+      python3 scripts/pmc_instmix.py "render_stream_kernel" \
+        "$(dirname "${dirs[0]}")/profiles_${R}/${R}_instmix_headline${suf}_stream.json" "${dirs[@]}"
+      continue
+    fi
     python3 scripts/pmc_instmix.py "render_kernel<false, true, false, false>" gpurun_out/profiles_${R}/${R}_instmix_headline${suf}.json "${dirs[@]}"
   fi
 done

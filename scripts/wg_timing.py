@@ -2,7 +2,9 @@
 """Per-workgroup timing of an RT_WG_TIMING build (dev tool).
 
 usage: RTGO_LIB=.../librtgo_timing.so wg_timing.py [scene.json] [W H SPP]
-Prints the kernel span, wave duration percentiles, how many waves are in
+WG_FRAMES=N (N >= 2) times one batched launch of N frames
+(rt_context_render_frames_async: the batched block_work default) instead of a
+one-frame launch.  Prints the kernel span, wave duration percentiles, how many waves are in
 flight over time (occupancy profile) and the slowest workgroups' tiles.
 """
 import os
@@ -32,9 +34,10 @@ else:
     ctx.set_scene(rtgo.Scene.load_from_file(scene))
 st = rtgo.default_settings()
 st.samples = SPP
-lin = torch.zeros(W * H * 3, dtype=torch.float32, device="cuda")
-rgba = torch.zeros(W * H * 4, dtype=torch.uint8, device="cuda")
-nwg_max = 200_000
+FRAMES = int(os.environ.get("WG_FRAMES", "1"))
+lin = torch.zeros((FRAMES, W * H * 3), dtype=torch.float32, device="cuda")
+rgba = torch.zeros((FRAMES, W * H * 4), dtype=torch.uint8, device="cuda")
+nwg_max = max(200_000, 20_000 * FRAMES)
 dbg = torch.zeros(nwg_max * 48, dtype=torch.int64, device="cuda")
 ctx.set_debug_buffer(dbg.data_ptr())
 RANK, WORLD = int(os.environ.get("WG_RANK", "0")), int(os.environ.get("WG_WORLD", "1"))
@@ -44,10 +47,16 @@ for _ in range(2):
     e0 = torch.cuda.Event(enable_timing=True)
     e1 = torch.cuda.Event(enable_timing=True)
     e0.record()
-    ctx.render_async(W, H, st, lin.data_ptr(), rgba.data_ptr(), 0, RANK, WORLD, rtgo.RT_LAYOUT_PACKED_TILES)
+    if FRAMES > 1:
+        ctx.render_frames_async(W, H, st, list(range(1, FRAMES + 1)), [lin[f].data_ptr() for f in range(FRAMES)],
+                                [rgba[f].data_ptr() for f in range(FRAMES)], 0, RANK, WORLD,
+                                rtgo.RT_LAYOUT_PACKED_TILES)
+    else:
+        ctx.render_async(W, H, st, lin.data_ptr(), rgba.data_ptr(), 0, RANK, WORLD, rtgo.RT_LAYOUT_PACKED_TILES)
     e1.record()
     torch.cuda.synchronize()
-print(f"kernel {e0.elapsed_time(e1):.3f} ms (rank {RANK}/{WORLD}, depth {st.max_depth})")
+print(f"kernel {e0.elapsed_time(e1):.3f} ms (rank {RANK}/{WORLD}, depth {st.max_depth}, frames {FRAMES}: "
+      f"{e0.elapsed_time(e1) / FRAMES:.3f} ms per frame)")
 WPG = int(os.environ.get("WG_WAVES", "1"))  # waves per workgroup of the kernel
 d = dbg.cpu().numpy().reshape(-1, WPG, 48)
 used = d[:, 0, 0] != 0
@@ -127,6 +136,10 @@ print(f"  WGs that ran a lone path (solo_path): {int(solo.sum())} of {nwg}; entr
       f"lone-path bounces {int(d[:, 0, 42].sum())}")
 busy = dur.sum()
 print(f"  mean waves in flight {busy / span:.1f}")
+# workgroups that shade nothing (black blocks, and blocks whose camera rays all miss)
+idle = it[:, 0] == 0
+print(f"  WGs without a shade iteration: {int(idle.sum())} of {nwg}; their share of wave time "
+      f"{(end - start)[idle].sum() / max(busy, 1e-9):.1%} (mean {(end - start)[idle].mean() if idle.any() else 0:.2f} us)")
 bclk = d[:, 0, 32:37].astype(np.float64)
 bcnt = d[:, 0, 37:42].astype(np.float64)
 names = ["1", "2", "3-4", "5-8", ">8"]
