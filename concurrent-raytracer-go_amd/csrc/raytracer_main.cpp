@@ -4,6 +4,7 @@
 //             [--samples N] [--max-depth N] [--seed N] [--no-soft-shadows]
 //             [--no-recursive] [--devices N] [--watchdog SECONDS]
 //             [--sky default|white|sunset|night]
+//             [--pass-samples N [--time-budget SECONDS] [--converge PIXELS]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -13,7 +14,12 @@
 // gains the published rays_per_second / pixels_per_second fields
 // (README.md:60-61), and the optional flags above (the Go CLI never calls
 // the renderer's setters, settings.go:3-25; --sky is the opt-in atmosphere,
-// include/rt_api.h RT_SKY_*).
+// include/rt_api.h RT_SKY_*).  --pass-samples N renders progressively on one
+// device: N samples per pass up to the cap --samples, one
+// "Pass k: n samples[, c pixels changed]" line per pass, stopping early once
+// --time-budget SECONDS have passed or at most --converge PIXELS pixels of the
+// preview changed in a pass; the output is written once, at the end, and
+// benchmark_data.json records the samples actually rendered.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,9 +29,12 @@
 #include <time.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "../../include/rt_api.h"
 
@@ -137,9 +146,87 @@ static void save_benchmark(const std::string& out_path, long long w, long long h
   }
 }
 
+// --pass-samples: the frame through rt_context_progressive_* on device 0,
+// pass_samples at a time up to the cap st.samples; fills rgba (host, w*h*4),
+// stats and *rendered (samples per pixel actually rendered).  budget_s < 0 /
+// converge < 0: that rule is off.
+static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int pass_samples,
+                              double budget_s, long long converge, uint8_t* rgba, rt_stats* stats, int* rendered) {
+  const auto t_new = std::chrono::steady_clock::now();
+  rt_context* ctx = nullptr;
+  if (rt_context_create(0, &ctx) != RT_OK) return RT_E_DEVICE;
+  stats->create_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_new).count();
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t npix = (size_t)w * (size_t)h;
+  uint8_t* d_img[2] = {nullptr, nullptr};
+  uint32_t* d_delta = nullptr;
+  int rc = rt_context_set_scene(ctx, scene, 0);
+  stats->scene_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  auto hip_ok = [&](hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    fprintf(stderr, "%s failed: %s\n", what, hipGetErrorString(e));
+    rc = RT_E_DEVICE;
+    return false;
+  };
+  if (rc == RT_OK) rc = rt_context_progressive_begin(ctx, w, h, &st, 0, 1, RT_LAYOUT_IMAGE);
+  if (rc == RT_OK && hip_ok(hipMalloc((void**)&d_img[0], npix * 4), "hipMalloc") &&
+      hip_ok(hipMalloc((void**)&d_img[1], npix * 4), "hipMalloc"))
+    hip_ok(hipMalloc((void**)&d_delta, 2 * sizeof(uint32_t)), "hipMalloc");
+  int done = 0, k = 0;
+  double kernel_s = 0;
+  while (rc == RT_OK) {
+    const int n = std::min(pass_samples, st.samples - done);
+    uint8_t* cur = d_img[k & 1];
+    rc = rt_context_progressive_add_async(ctx, n, nullptr, cur, nullptr);
+    if (rc != RT_OK) break;
+    uint32_t delta[2] = {0, 0};
+    if (k > 0) {  // how much the preview still moved in this pass
+      rc = rt_rgba_delta_async(d_img[(k & 1) ^ 1], cur, npix, d_delta, nullptr);
+      if (rc != RT_OK) break;
+      if (!hip_ok(hipMemcpy(delta, d_delta, sizeof delta, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+    } else if (!hip_ok(hipStreamSynchronize(nullptr), "hipStreamSynchronize")) {
+      break;
+    }
+    double ks = 0;
+    if (rt_context_last_kernel_seconds(ctx, &ks) == RT_OK) kernel_s += ks;
+    done += n;
+    k += 1;
+    if (k > 1)
+      printf("Pass %d: %d samples, %u pixels changed\n", k, done, delta[0]);
+    else
+      printf("Pass %d: %d samples\n", k, done);
+    fflush(stdout);
+    const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (done >= st.samples || (budget_s >= 0 && el >= budget_s) || (converge >= 0 && k > 1 && (long long)delta[0] <= converge))
+      break;
+  }
+  if (rc == RT_OK && k > 0)
+    hip_ok(hipMemcpy(rgba, d_img[(k - 1) & 1], npix * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+  const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
+  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  (void)rt_context_progressive_end(ctx);
+  for (void* p : {(void*)d_img[0], (void*)d_img[1], (void*)d_delta})
+    if (p) (void)hipFree(p);
+  rt_context_destroy(ctx);
+  if (rc != RT_OK) {
+    if (!err.empty()) fprintf(stderr, "%s\n", err.c_str());
+    return rc;
+  }
+  *rendered = done;
+  stats->render_seconds = secs;
+  stats->kernel_seconds = kernel_s;
+  stats->objects = scene->num_objects;
+  stats->lights = scene->num_lights;
+  stats->rays_per_second = (double)npix * done / secs;
+  stats->pixels_per_second = (double)npix / secs;
+  return RT_OK;
+}
+
 int main(int argc, char** argv) {
   std::vector<std::string> args;
   double watchdog_s = 0;  // --watchdog (0: no bound, as Go's Render)
+  long long pass_samples = 0, converge = -1;  // --pass-samples (0: one render), --converge (-1: off)
+  double budget_s = -1;                       // --time-budget (-1: off)
   rt_settings st;
   rt_settings_default(&st);
   st.num_workers = (int32_t)sysconf(_SC_NPROCESSORS_ONLN);  // runtime.NumCPU(), main.go:46
@@ -177,6 +264,28 @@ int main(int argc, char** argv) {
         fprintf(stderr, "invalid --watchdog %s\n", x);
         return 2;
       }
+    } else if (a == "--pass-samples") {  // progressive: N samples per pass, --samples is the cap
+      const char* x = need("--pass-samples");
+      if (!parse_int(x, &v) || v < 1 || v > (1 << 24)) {
+        fprintf(stderr, "invalid --pass-samples %s\n", x);
+        return 2;
+      }
+      pass_samples = v;
+    } else if (a == "--time-budget") {  // progressive: stop after the pass at which SECONDS have passed
+      const char* x = need("--time-budget");
+      char* end = nullptr;
+      budget_s = strtod(x, &end);
+      if (!end || end == x || *end || !(budget_s >= 0)) {
+        fprintf(stderr, "invalid --time-budget %s\n", x);
+        return 2;
+      }
+    } else if (a == "--converge") {  // progressive: stop once a pass changed at most PIXELS pixels
+      const char* x = need("--converge");
+      if (!parse_int(x, &v) || v < 0) {
+        fprintf(stderr, "invalid --converge %s\n", x);
+        return 2;
+      }
+      converge = v;
     } else if (a == "--sky") {  // opt-in sky on miss (atmosphere.go presets); default: black
       const std::string k = need("--sky");
       if (k == "none") st.sky = RT_SKY_NONE;
@@ -191,6 +300,18 @@ int main(int argc, char** argv) {
     } else {
       args.push_back(a);
     }
+  }
+  if (pass_samples > 0 && st.num_devices > 1) {
+    fprintf(stderr, "--pass-samples renders on one device (--devices %d)\n", st.num_devices);
+    return 2;
+  }
+  if (pass_samples > 0 && st.samples < 1) {
+    fprintf(stderr, "--pass-samples needs --samples >= 1 (the cap)\n");
+    return 2;
+  }
+  if (pass_samples == 0 && (budget_s >= 0 || converge >= 0)) {
+    fprintf(stderr, "--time-budget and --converge need --pass-samples\n");
+    return 2;
   }
   if (args.size() < 4) {
     printf("Usage: raytracer <scene_file> <output_file> <width> <height>\n");
@@ -258,6 +379,39 @@ int main(int argc, char** argv) {
       return 1;
     }
     save_benchmark(out_path, w, h, st, stats);
+    rt_scene_free(sb);
+    return 0;
+  }
+  if (pass_samples > 0) {
+    printf("Rendering at %lldx%lld resolution...\n", w, h);
+    fflush(stdout);
+    rt_scene_print_hittables(sb);
+    std::vector<uint8_t> rgba((size_t)w * (size_t)h * 4);
+    rt_stats stats;
+    memset(&stats, 0, sizeof stats);
+    int rendered = 0;
+    if (rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK ||
+        render_progressive(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)pass_samples, budget_s, converge,
+                           rgba.data(), &stats, &rendered) != RT_OK) {
+      fprintf(stderr, "render failed: %s\n", rt_last_error());
+      rt_scene_free(sb);
+      return 2;
+    }
+    print_complete();
+    std::string out_path = output_file;
+    if (ext_of(out_path).empty()) out_path += ".png";
+    printf("Saving to: %s\n", out_path.c_str());
+    fflush(stdout);
+    const int rc = ext_of(out_path) == ".ppm" ? rt_write_ppm(out_path.c_str(), rgba.data(), (int32_t)w, (int32_t)h)
+                                              : rt_write_png(out_path.c_str(), rgba.data(), (int32_t)w, (int32_t)h);
+    if (rc != RT_OK) {
+      printf("Error saving image: %s\n", rt_last_error());
+      rt_scene_free(sb);
+      return 1;
+    }
+    rt_settings done_st = st;
+    done_st.samples = rendered;  // (the samples actually rendered)
+    save_benchmark(out_path, w, h, done_st, stats);
     rt_scene_free(sb);
     return 0;
   }

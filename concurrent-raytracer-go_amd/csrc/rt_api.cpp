@@ -199,6 +199,15 @@ struct rt_context {
   char* d_rows = nullptr;
   size_t rows_cap = 0;
   int32_t wave_slots = 0;  // resident waves of render_stream_kernel on this device (its grid)
+  // a progression: its frame (prog_st.samples: the cap), the
+  // samples of every pixel done so far, and its own per-pixel running sums
+  // (KParams.acc layout; not d_acc, which ordinary sample passes use)
+  bool prog_on = false;
+  int32_t prog_w = 0, prog_h = 0, prog_rank = 0, prog_world = 1, prog_layout = 0;
+  rt_settings prog_st{};
+  int64_t prog_done = 0;
+  void* d_prog = nullptr;
+  size_t prog_cap = 0;
 };
 
 // Events for kernel classes [first, last] of one launch sequence: ev[k] opens
@@ -336,6 +345,7 @@ int rt_context_set_tuning(rt_context* c, const rt_tuning* t) {
   }
   c->tun = *t;
   c->order_key[0] = -1;  // rebuild the schedule
+  c->prog_on = false;    // (a progression ends: its next add is refused)
   return RT_OK;
 }
 
@@ -462,7 +472,7 @@ void rt_context_destroy(rt_context* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_scene, (void*)c->d_counts, (void*)c->d_blocks, (void*)c->d_pilot, c->d_acc,
                   (void*)c->d_meas, (void*)c->d_split, (void*)c->d_sched, (void*)c->d_part, c->wf_mem, c->wf_rad,
-                  (void*)c->wf_ctl, (void*)c->d_tail, (void*)c->d_live, (void*)c->d_rows})
+                  (void*)c->wf_ctl, (void*)c->d_tail, (void*)c->d_live, (void*)c->d_rows, c->d_prog})
     dev_free(p);
   host_free(c->h_stage);
   host_free(c->h_small);
@@ -492,6 +502,7 @@ int rt_context_set_scene(rt_context* c, const rt_scene* s, int32_t force_bvh) {
   int rc = validate_scene(s);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
+  c->prog_on = false;  // (a progression ends with its scene)
   flatten_scene(*s, &c->flat);
   c->bvh_seconds = 0;
   const bool want_bvh = force_bvh > 0 || (force_bvh == 0 && c->flat.spheres.size() > 64);
@@ -822,9 +833,14 @@ static double default_block_work(const rt_context* c, int frames = 1) {
 // primary-ray candidate masks apply (small linear-scan scenes)
 static bool masks_apply(const FlatScene& f) { return f.bvh.empty() && f.spheres.size() <= 64 && f.tris.size() <= 64; }
 
+// KParams.acc_mode of a progression's add that is one launch (DESIGN.md
+// §4.8): start from the sums, keep them, write the image
+constexpr int32_t kAccProgressive = 1 | 4;
+
 // Could a render of these settings be streamed?  A staged
-// linear-scan scene, no sky, one sample pass, tail helpers off, no measured
-// schedule; `frames`: the frames per launch of the schedule's key.
+// linear-scan scene, no sky, one sample pass (or a progression's add of one
+// launch), tail helpers off, no measured schedule; `frames`: the frames per
+// launch of the schedule's key.
 static bool stream_wanted(const rt_context* c, const KParams& p, const rt_settings* st, int frames) {
   const rt_tuning& tn = c->tun;
   // auto: launches of several frames of sphere-only scenes, where the A/B shows a
@@ -833,7 +849,8 @@ static bool stream_wanted(const rt_context* c, const KParams& p, const rt_settin
   // pass only the block's frustum candidates)
   if (tn.stream == 0 || (tn.stream < 0 && (frames < 2 || !c->flat.tris.empty()))) return false;
   return tn.stage && c->stage_bytes > 0 && c->flat.bvh.empty() && st->sky == RT_SKY_NONE && st->samples >= 1 &&
-         st->samples <= kMaxBlockSamples && p.spp_total == st->samples && tn.tail_helpers < 0 && !tn.measure;
+         st->samples <= kMaxBlockSamples && (p.spp_total == st->samples || p.acc_mode == kAccProgressive) &&
+         tn.tail_helpers < 0 && !tn.measure;
 }
 
 static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream_t s, int frames = 1) {
@@ -1107,6 +1124,11 @@ static int render_wavefront(rt_context* c, const KParams& kp, const rt_settings*
   p.recursive = kp.recursive;
   p.soft = kp.soft;
   p.spp = st->samples;  // (0: the mean is 0/0 = NaN, as DivScalar(0) in Go)
+  // a progression's add: samples [sample_base, sample_base +
+  // spp) of spp_total, the resolve continuing the sums; else 0, spp, none
+  p.sample_base = kp.sample_base;
+  p.spp_total = kp.spp_total;
+  p.acc = (kp.acc_mode & 4) ? kp.acc : nullptr;
   p.W = kp.W;
   p.H = kp.H;
   p.rank = kp.rank;
@@ -1249,7 +1271,9 @@ static int render_wavefront(rt_context* c, const KParams& kp, const rt_settings*
 static int render_stream(rt_context* c, const KParams& p, const rt_settings* st, int nframes, int key_frames,
                          hipStream_t s, bool* streamed) {
   *streamed = false;
-  if (!stream_wanted(c, p, st, key_frames) || c->nlive < 0 || p.counts || p.work_max || p.acc_mode != 0 || p.sky)
+  const bool prog = p.acc_mode == kAccProgressive && nframes == 1;
+  if (!stream_wanted(c, p, st, key_frames) || c->nlive < 0 || p.counts || p.work_max || (p.acc_mode != 0 && !prog) ||
+      p.sky)
     return RT_OK;
   const rt_tuning& tn = c->tun;
   const size_t budget = (size_t)((tn.stream_max_mb > 0 ? tn.stream_max_mb : 1024.0) * 1048576.0);
@@ -1277,6 +1301,7 @@ static int render_stream(rt_context* c, const KParams& p, const rt_settings* st,
   sp.npix = c->live_local * 1024;
   sp.chunk = tn.stream_chunk > 0 ? tn.stream_chunk : 512;
   sp.order = tn.stream_order;
+  sp.acc = prog ? p.acc : nullptr;  // (the resolve continues the progression's sums)
   for (int f0 = 0; f0 < nframes; f0 += group) {
     sp.frame0 = f0;
     sp.frames = std::min(group, nframes - f0);
@@ -1442,6 +1467,7 @@ int rt_context_set_partition(rt_context* c, const rt_partition* p) {
   HIP_TRY(hipSetDevice(c->device));
   int rc = quiesce(c);  // the last render may still read the tile lists
   if (rc) return rc;
+  c->prog_on = false;  // (a progression's tiles are those of its begin: it ends)
   if (!p) {
     c->part.reset();
     return RT_OK;
@@ -1754,6 +1780,146 @@ int rt_context_render_frames_async(rt_context* c, int32_t w, int32_t h, const rt
   c->stats.frames += nframes;
   c->stats.launches += 1;
   c->stats.batched_launches += 1;
+  return RT_OK;
+}
+
+// ------------------------------------------------------------ progressive rendering
+//  The random streams are keyed by (seed, pixel, sample), so
+// samples [done, done + n) of a pixel do not depend on how many follow; an add
+// renders them and continues the pixel's binary64 sum in sample order, as the
+// sample passes of a frame of more than kMaxBlockSamples do.
+int rt_context_progressive_begin(rt_context* c, int32_t w, int32_t h, const rt_settings* st, int32_t rank,
+                                 int32_t world, int32_t layout) {
+  if (!c || !c->have_scene) {
+    set_error("context has no scene");
+    return RT_E_INVALID;
+  }
+  int rc = validate_settings(st, w, h);
+  if (rc) return rc;
+  if (world < 1 || rank < 0 || rank >= world) {
+    set_error("invalid rank/world");
+    return RT_E_INVALID;
+  }
+  if (layout != RT_LAYOUT_IMAGE && layout != RT_LAYOUT_PACKED_TILES) {
+    set_error("invalid layout");
+    return RT_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  c->prog_on = false;
+  rc = quiesce(c);  // an add of the progression this one replaces may still use the sums
+  if (rc) return rc;
+  const size_t bytes = std::max<size_t>((size_t)local_tiles(c, w, h, rank, world) * 1024 * 3 * sizeof(double), 256);
+  rc = grow(c, &c->d_prog, &c->prog_cap, bytes);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(c->d_prog, 0, bytes, c->stream));
+  rc = wait_stream(c, c->stream);
+  if (rc) return rc;
+  c->prog_w = w;
+  c->prog_h = h;
+  c->prog_rank = rank;
+  c->prog_world = world;
+  c->prog_layout = layout;
+  c->prog_st = *st;
+  c->prog_done = 0;
+  c->prog_on = true;
+  return RT_OK;
+}
+
+int rt_context_progressive_add_async(rt_context* c, int32_t nsamples, float* d_linear, uint8_t* d_rgba,
+                                     void* stream) {
+  if (!c || !c->prog_on || !c->have_scene) {
+    set_error("rt_context_progressive_add_async: the context has no progression (none begun, or it was ended)");
+    return RT_E_INVALID;
+  }
+  if (nsamples < 1 || c->prog_done + nsamples > c->prog_st.samples) {
+    set_error("rt_context_progressive_add_async: nsamples must be >= 1 and stay within the cap (" +
+              std::to_string(c->prog_done) + " of " + std::to_string(c->prog_st.samples) + " done)");
+    return RT_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const rt_settings* st = &c->prog_st;
+  const int w = c->prog_w, h = c->prog_h, rank = c->prog_rank, world = c->prog_world;
+  KParams p;
+  base_params(c, w, h, st, rank, world, c->prog_layout, &p);
+  p.out_linear = d_linear;
+  p.out_rgba = d_rgba;
+  hipStream_t s = (hipStream_t)stream;
+  if (c->have_timing && s != c->last_stream) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
+  const bool wf = use_wavefront(c);
+  // more than a block holds: sub-passes, as a frame's sample passes (render_one);
+  // only the last one writes the image
+  const int npass = wf ? 1 : (nsamples + kMaxBlockSamples - 1) / kMaxBlockSamples;
+  const int done = (int)c->prog_done;
+  p.acc = (double*)c->d_prog;
+  p.spp_total = done + nsamples;  // the divisor of the mean
+  for (int pass = 0; pass < npass; ++pass) {
+    rt_settings ps = *st;
+    const int s0 = (int)((long long)nsamples * pass / npass), s1 = (int)((long long)nsamples * (pass + 1) / npass);
+    ps.samples = s1 - s0;
+    p.spp = ps.samples;
+    p.sample_base = done + s0;
+    // (the sums start at zero, so the first add continues them like any other)
+    p.acc_mode = 1 | (pass < npass - 1 ? 2 : 4);
+    if (!wf) {
+      // (keyed by the add's sample count, not by sample_base: equal adds share a schedule)
+      int rc = prepare_schedule(c, &p, &ps, s, 1);
+      if (rc) return rc;
+    }
+    p.num_wgs = p.num_blocks;
+    if (pass == 0) HIP_TRY(hipEventRecord(c->ev0, s));
+    if (wf) {
+      int rc = render_wavefront(c, p, &ps, s, false);
+      if (rc) return rc;
+    } else {
+      bool streamed = false;
+      if (npass == 1) {
+        int rc = render_stream(c, p, &ps, 1, 1, s, &streamed);
+        if (rc) return rc;
+      }
+      const int e = streamed ? (int)hipSuccess : launch_render(p, false, s);
+      if (e != hipSuccess) {
+        set_error(std::string("render launch failed: ") + hipGetErrorString((hipError_t)e));
+        return RT_E_DEVICE;
+      }
+    }
+  }
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->stats.frames += 1;
+  c->stats.launches += npass;
+  c->last_stream = s;
+  c->have_timing = true;
+  c->prog_done += nsamples;
+  return RT_OK;
+}
+
+int64_t rt_context_progressive_samples(const rt_context* c) { return c && c->prog_on ? c->prog_done : -1; }
+
+int rt_context_progressive_end(rt_context* c) {
+  if (!c) {
+    set_error("context is NULL");
+    return RT_E_INVALID;
+  }
+  c->prog_on = false;
+  if (!c->d_prog) return RT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = quiesce(c);  // the last add may still use the sums
+  if (rc) return rc;
+  dev_free(c->d_prog);
+  c->d_prog = nullptr;
+  c->prog_cap = 0;
+  return RT_OK;
+}
+
+int rt_rgba_delta_async(const uint8_t* d_a, const uint8_t* d_b, size_t npix, uint32_t* d_out, void* stream) {
+  if (!d_out || (npix > 0 && (!d_a || !d_b))) {
+    set_error("rt_rgba_delta_async: NULL buffer");
+    return RT_E_INVALID;
+  }
+  const int e = launch_rgba_delta(d_a, d_b, npix, d_out, stream);
+  if (e != hipSuccess) {
+    set_error(std::string("rgba delta launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RT_E_DEVICE;
+  }
   return RT_OK;
 }
 

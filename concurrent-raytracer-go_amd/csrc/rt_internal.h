@@ -247,6 +247,8 @@ struct KParams {
   // 3 doubles) between passes.  acc_mode: bit 0 = start from acc (not the
   // first pass), bit 1 = store the sum to acc instead of writing the image
   // (not the last pass).  Single pass: acc_mode 0, spp_total = spp.
+  // Bit 2 (a progression's add): store the sum to acc AND
+  // write the image, the mean over spp_total = samples done + this add's.
   double* acc;
   int32_t sample_base, spp_total, acc_mode;
   // FRAMES of one launch (rt_context_render_frames_async): the same schedule
@@ -294,6 +296,9 @@ struct StreamParams {
   int32_t nlive, npix;         // live pixels; local pixels (local tiles * 1024)
   int32_t frame0, frames;      // the launch's frames [frame0, frame0 + frames) of KParams::frame_*
   int32_t chunk, order;        // entries per claim; the entry order
+  // a progression's add: each local pixel's running sum
+  // (KParams::acc layout), which the resolve continues and stores back; null: from +0
+  double* acc;
 };
 struct StreamKArgs {           // the kernels' one argument: KParams at offset 0 (rt_kernel.hip fresh())
   KParams k;
@@ -317,6 +322,9 @@ int launch_spin(double ms, void* stream);
 int partition_balanced(rt_context* c, int32_t w, int32_t h, const rt_settings* st, int32_t world, int measure_spp,
                        rt_partition** out);
 constexpr int kRendererPartitionSpp = 16;
+// d_out[0] = pixels of a, b (RGBA8, npix each) that differ, d_out[1] = the
+// largest byte difference; zeroes d_out on the stream first (rt_rgba_delta_async)
+int launch_rgba_delta(const uint8_t* d_a, const uint8_t* d_b, size_t npix, uint32_t* d_out, void* stream);
 int launch_unpack(int32_t W, int32_t H, int32_t world, const void* gathered, size_t share_bytes, size_t rgba_off,
                   float* ol, uint8_t* orgba, void* stream);
 // The same for a partition: slot[t] = {owner rank, local tile} of global tile t;
@@ -420,6 +428,11 @@ struct WfParams {
   unsigned long long* counts;
   float* out_linear;
   uint8_t* out_rgba;
+  // a progression's add: the chunk's sample s of a pixel is
+  // the frame's sample sample_base + s; wf_resolve continues the pixel's sum
+  // in acc (KParams::acc layout; null: from +0) and divides by spp_total
+  double* acc;
+  int32_t sample_base, spp_total;
 };
 // Kernel classes of one bounce (rt_context_profile): prof, when not null,
 // holds kWfProfEvents hipEvent_t recorded at their boundaries (event k opens

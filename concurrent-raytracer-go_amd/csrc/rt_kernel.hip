@@ -1379,8 +1379,10 @@ __device__ __forceinline__ SArg sfresh() {
 // long as there are any, with the SAME bounce code; a path's running L lives
 // in its lane's slot, and its final value goes to its row in global memory
 // (resolve_rows_kernel sums the rows).  The block-only LDS arrays shrink to
-// one element there.
-template <bool kCount, bool kStage, bool kPilot, bool kSky, bool kTailT, bool kStream = false>
+// one element there.  kBase (render_stream_base_kernel): entry
+// sample s is the frame's sample sample_base + s (a progression's later adds);
+// an instantiation of its own, so the product stream kernel keeps its code.
+template <bool kCount, bool kStage, bool kPilot, bool kSky, bool kTailT, bool kStream = false, bool kBase = false>
 __device__ __forceinline__ void render_body(const KParams& pk) {
   static_assert(!kStream || (kStage && !kCount && !kPilot && !kSky && !kTailT), "the stream kernel is the staged product body");
   __shared__ uint32_t hbits[kStream ? 1 : kMaxBlockSamples / 32];  // hit samples of the block
@@ -1772,10 +1774,12 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               const uint64_t fkey = sk->k.frame_key[sk->s.frame0 + (int)fl];
               Counters nc;
               // the camera ray and the soft-shadow key exactly as the block
-              // kernel's refill below builds them
+              // kernel's refill below builds them (kBase: the frame's sample
+              // sample_base + s, a progression's add)
+              const unsigned fs = kBase ? (unsigned)sk->k.sample_base + s : s;
               camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, sk->k.aspect, sk->k.cam[0], sk->k.cam[1], sk->k.cam[2]),
-                                  it.x, it.y, (int)s, rng, o, d, nc);
-              skey[lane_now()] = rt_soft_key(fkey, (uint32_t)it.y * (uint32_t)sk->k.W + (uint32_t)it.x, (uint32_t)s);
+                                  it.x, it.y, (int)fs, rng, o, d, nc);
+              skey[lane_now()] = rt_soft_key(fkey, (uint32_t)it.y * (uint32_t)sk->k.W + (uint32_t)it.x, (uint32_t)fs);
               entry = (int)((fl * spp + s) * nlive + i);
               T = mk(1, 1, 1);
               set_path_L(mk(0, 0, 0));
@@ -2355,6 +2359,12 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
       a[1] = psum[p][1];
       a[2] = psum[p][2];
     } else if (p < loc.np && tp < 1024 && loc.tile < k->ntiles && x < k->W && y < k->H) {
+      if (k->acc_mode & 4) {  // a progression's add: keep the sum and write the pixel
+        double* a = k->acc + ((size_t)loc.lt * 1024 + tp) * 3;
+        a[0] = psum[p][0];
+        a[1] = psum[p][1];
+        a[2] = psum[p][2];
+      }
       const double n = (double)k->spp_total;
       const double mx = psum[p][0] / n, my = psum[p][1] / n, mz = psum[p][2] / n;  // DivScalar(float64(samples))
       const size_t oi = k->layout == RT_LAYOUT_IMAGE ? (size_t)y * k->W + x : (size_t)loc.lt * 1024 + (size_t)tp;
@@ -2456,6 +2466,11 @@ __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_kernel_tail(cons
 __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_stream_kernel(const StreamKArgs a) {
   render_body<false, true, false, false, false, true>(a.k);
 }
+// The same with KParams::sample_base added to every entry's sample index (a
+// progression's adds after its first).
+__global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_stream_base_kernel(const StreamKArgs a) {
+  render_body<false, true, false, false, false, true, true>(a.k);
+}
 // After it on the same stream: one lane per pixel of the rank's tiles, per
 // frame of the launch (blockIdx.y).  Lane t writes local pixel t black when it
 // is not live (what the block kernel's epilogue writes for it: a sum of +0),
@@ -2480,11 +2495,24 @@ __global__ __launch_bounds__(256) void resolve_rows_kernel(const StreamKArgs a) 
     const size_t nlive = (size_t)sk->s.nlive;
     const int spp = k->spp;
     const double* __restrict__ row = sk->s.rows + ((size_t)fl * spp * nlive + t) * 3;
+    // (a progression's add, one frame: the pixel's sum over the earlier
+    // samples is continued and stored back)
+    double* const acc = sk->s.acc ? sk->s.acc + (size_t)it.w * 3 : nullptr;
     double sx = 0, sy = 0, sz = 0;
+    if (acc) {
+      sx = acc[0];
+      sy = acc[1];
+      sz = acc[2];
+    }
     for (int s = 0; s < spp; ++s, row += nlive * 3) {
       sx += row[0];
       sy += row[1];
       sz += row[2];
+    }
+    if (acc) {
+      acc[0] = sx;
+      acc[1] = sy;
+      acc[2] = sz;
     }
     store_pixel(k, fr, k->layout == RT_LAYOUT_IMAGE ? (size_t)(uint32_t)it.z : (size_t)it.w, sx, sy, sz);
   }
@@ -2512,7 +2540,10 @@ int launch_stream(const KParams& pin, const StreamParams& sp, int wgs, void* str
   if (p.stage_bytes <= 0 || p.use_bvh || wgs <= 0 || sp.frames <= 0 || sp.npix <= 0) return (int)hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(sp.cursor, 0, sizeof(unsigned int), st);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(render_stream_kernel, dim3(wgs), dim3(64), render_shmem(p), st, a);
+  if (p.sample_base != 0)
+    hipLaunchKernelGGL(render_stream_base_kernel, dim3(wgs), dim3(64), render_shmem(p), st, a);
+  else
+    hipLaunchKernelGGL(render_stream_kernel, dim3(wgs), dim3(64), render_shmem(p), st, a);
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(resolve_rows_kernel, dim3((unsigned)((sp.npix + 255) / 256), (unsigned)sp.frames), dim3(256), 0, st, a);
@@ -2567,6 +2598,54 @@ __global__ __launch_bounds__(256) void unpack_map_kernel(int W, int H, int tiles
   }
   if (orgba)
     *reinterpret_cast<uint32_t*>(orgba + oo * 4) = *reinterpret_cast<const uint32_t*>(share + rgba_off + pi * 4);
+}
+
+// How much two RGBA8 images differ (rt_rgba_delta_async): out[0] += pixels
+// whose four bytes are not all equal, out[1] = max(out[1], the largest byte
+// difference).  One lane per pixel and step, one 32-bit load per image; a
+// wave counts its differing pixels with a ballot (wave-uniform, every lane of
+// the wave runs every step) and keeps each lane's largest difference, reduced
+// across the wave once at the end: one add and one max per wave (none from a
+// wave that saw no difference).  Integers only, so the result does not depend
+// on the order.  Grid-stride: any npix.
+__global__ __launch_bounds__(256) void rgba_delta_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                         size_t npix, uint32_t* __restrict__ out) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t lane = threadIdx.x & 63u;
+  // the wave's first pixel of each step (wave-uniform, so is the trip count)
+  size_t base = (size_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u);
+  unsigned int changed = 0, dmax = 0;
+  for (; base < npix; base += stride) {
+    const size_t i = base + lane;
+    unsigned int d = 0;
+    bool diff = false;
+    if (i < npix) {
+      const uint32_t va = a[i], vb = b[i];
+      diff = va != vb;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int x = (int)((va >> (8 * c)) & 255u), y = (int)((vb >> (8 * c)) & 255u);
+        d = max(d, (unsigned int)(x > y ? x - y : y - x));
+      }
+    }
+    changed += (unsigned int)__popcll(__ballot(diff));
+    dmax = max(dmax, d);
+  }
+  for (int off = 32; off >= 1; off >>= 1) dmax = max(dmax, __shfl_xor(dmax, off));
+  if (lane == 0 && changed != 0) {
+    atomicAdd(&out[0], changed);
+    atomicMax(&out[1], dmax);
+  }
+}
+
+int launch_rgba_delta(const uint8_t* d_a, const uint8_t* d_b, size_t npix, uint32_t* d_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(d_out, 0, 2 * sizeof(uint32_t), st);
+  if (e != hipSuccess || npix == 0) return (int)e;
+  const unsigned grid = (unsigned)((npix + 255) / 256 < 2048 ? (npix + 255) / 256 : 2048);
+  hipLaunchKernelGGL(rgba_delta_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(d_a),
+                     reinterpret_cast<const uint32_t*>(d_b), npix, d_out);
+  return (int)hipGetLastError();
 }
 
 size_t render_shmem(const KParams& p) {

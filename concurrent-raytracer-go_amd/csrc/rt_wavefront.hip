@@ -1106,7 +1106,7 @@ __device__ __forceinline__ uint64_t sid_soft_key(const WfParams& p, uint32_t sid
   const int lt = (int)(lp >> 10), tp = (int)(lp & 1023);
   const int tile = p.tile_list ? p.tile_list[lt] : p.rank + lt * p.world;
   const int x = (tile % p.tiles_x) * 32 + (tp & 31), y = (tile / p.tiles_x) * 32 + (tp >> 5);
-  return rt_soft_key(p.seed_key, (uint32_t)y * (uint32_t)p.W + (uint32_t)x, smp);
+  return rt_soft_key(p.seed_key, (uint32_t)y * (uint32_t)p.W + (uint32_t)x, (uint32_t)p.sample_base + smp);
 }
 
 // ---------------------------------------------------------------- softgen
@@ -1613,7 +1613,7 @@ __global__ __launch_bounds__(kWfBlock) void wf_regen(const WfParams p) {
         const CamK ck = make_cam(p.seed_key, p.W, p.H, p.aspect, p.cam[0], p.cam[1], p.cam[2]);
         rt_rng rng;
         d3 o, d;
-        camera_ray_c<kCount>(ck, x, y, smp, rng, o, d, c);
+        camera_ray_c<kCount>(ck, x, y, p.sample_base + smp, rng, o, d, c);
         store_path(p.next, slot, o, d, mk(1, 1, 1), mk(0, 0, 0), rng.x, sid, 0);
       }
     }
@@ -1662,13 +1662,25 @@ __global__ __launch_bounds__(kWfBlock) void wf_resolve(const WfParams p, int npi
   const int x = (tile % p.tiles_x) * 32 + (tp & 31), y = (tile / p.tiles_x) * 32 + (tp >> 5);
   if (tile >= p.ntiles || x >= p.W || y >= p.H) return;
   const double* r = p.rad + (size_t)q * p.spp * 3;
+  // (a progression's add continues the pixel's sum over the earlier samples)
+  double* const acc = p.acc ? p.acc + (size_t)lp * 3 : nullptr;
   double ax = 0, ay = 0, az = 0;
+  if (acc) {
+    ax = acc[0];
+    ay = acc[1];
+    az = acc[2];
+  }
   for (int s = 0; s < p.spp; ++s) {
     ax += r[3 * s + 0];
     ay += r[3 * s + 1];
     az += r[3 * s + 2];
   }
-  const double nn = (double)p.spp;
+  if (acc) {
+    acc[0] = ax;
+    acc[1] = ay;
+    acc[2] = az;
+  }
+  const double nn = (double)p.spp_total;
   const double mx = ax / nn, my = ay / nn, mz = az / nn;  // DivScalar(float64(samples))
   const size_t oi = p.layout == RT_LAYOUT_IMAGE ? (size_t)y * p.W + x : (size_t)lt * 1024 + (size_t)tp;
   if (p.out_linear) {

@@ -292,6 +292,11 @@ EXPORTED_SYMBOLS = [
     "rt_renderer_set_watchdog",
     "rt_renderer_test_stall",
     "rt_context_get_stats",
+    "rt_context_progressive_begin",
+    "rt_context_progressive_add_async",
+    "rt_context_progressive_samples",
+    "rt_context_progressive_end",
+    "rt_rgba_delta_async",
 ]
 
 _lib = None
@@ -395,6 +400,11 @@ def lib():
         "rt_context_get_stats": (ctypes.c_int, [vp, ctypes.POINTER(ContextStats)]),
         "rt_context_kernel_seconds": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double),
                                                      ctypes.POINTER(ctypes.c_int64)]),
+        "rt_context_progressive_begin": (ctypes.c_int, [vp, i32, i32, ctypes.POINTER(Settings), i32, i32, i32]),
+        "rt_context_progressive_add_async": (ctypes.c_int, [vp, i32, vp, vp, vp]),
+        "rt_context_progressive_samples": (ctypes.c_int64, [vp]),
+        "rt_context_progressive_end": (ctypes.c_int, [vp]),
+        "rt_rgba_delta_async": (ctypes.c_int, [vp, vp, sz, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -542,6 +552,8 @@ class ParallelRenderer:
         self.last_stats = None
         self._r = None  # the rt_renderer (made by the first render, kept like the Go object)
         self._tuning = None
+        self.last_samples = None  # samples per pixel of the last render_progressive
+        self._prog_ctx = None  # its Context (made by the first call, kept)
 
     def set_tuning(self, tuning: Tuning):
         self._tuning = tuning
@@ -565,6 +577,9 @@ class ParallelRenderer:
         if self._r is not None and _lib is not None:
             _lib.rt_renderer_destroy(self._r)
         self._r = None
+        if getattr(self, "_prog_ctx", None) is not None and _lib is not None:
+            self._prog_ctx.close()
+        self._prog_ctx = None
 
     def __del__(self):
         try:
@@ -660,6 +675,81 @@ class ParallelRenderer:
         }
         return rgba
 
+    def render_progressive(self, scene: Scene, width: int, height: int, pass_samples: int, time_budget=None,
+                           until_changed_pixels=None, on_pass=None) -> np.ndarray:
+        """Render the frame ``pass_samples`` samples at a time, on one device.
+
+        ``self.settings.samples`` is the cap; the last pass is clipped to it.
+        After each pass ``on_pass(samples_done, rgba, changed_pixels)`` is
+        called with the (H, W, 4) uint8 image of the samples so far and the
+        number of pixels that differ from the previous pass's image (None for
+        the first pass).  Stops after the first pass at which the cap is
+        reached, the wall time since the call began is >= ``time_budget``
+        (seconds), or ``changed_pixels <= until_changed_pixels``.  The image
+        after n samples is that of ``render`` with samples = n, byte for byte.
+        Returns the last image; ``last_linear`` holds its linear radiance and
+        ``last_samples`` the samples rendered.
+        """
+        t0 = time.perf_counter()
+        if (len(self.devices) if self.devices else max(1, self.settings.num_devices)) > 1:
+            raise RenderError("render_progressive renders on one device (multi-GPU progressions are not supported)")
+        cap = int(self.settings.samples)
+        if pass_samples < 1 or cap < 1:
+            raise RenderError("render_progressive: pass_samples and settings.samples must be >= 1")
+        _check(lib().rt_validate(ctypes.byref(scene.view), width, height, ctypes.byref(self.settings)))
+        import torch
+
+        dev = self.devices[0] if self.devices else 0
+        if self._prog_ctx is None:  # (a context of its own, kept like the rt_renderer)
+            self._prog_ctx = Context(dev)
+        ctx = self._prog_ctx
+        if self._tuning is not None:
+            ctx.set_tuning(self._tuning)
+        ctx.set_scene(scene)
+        npix = width * height
+        with torch.cuda.device(dev):
+            lin = torch.zeros(npix * 3, dtype=torch.float32, device="cuda")
+            bufs = [torch.zeros(npix * 4, dtype=torch.uint8, device="cuda") for _ in range(2)]
+            delta = torch.zeros(2, dtype=torch.int32, device="cuda")
+            ctx.progressive_begin(width, height, self.settings)
+            done, k, img = 0, 0, None
+            try:
+                while True:
+                    n = min(int(pass_samples), cap - done)
+                    cur, prev = bufs[k & 1], bufs[(k & 1) ^ 1]
+                    ctx.progressive_add(n, lin.data_ptr(), cur.data_ptr(), 0)
+                    if k > 0:  # how much the preview still moved in this pass
+                        rgba_delta_async(prev.data_ptr(), cur.data_ptr(), npix, delta.data_ptr(), 0)
+                    torch.cuda.synchronize()
+                    done += n
+                    img = cur.cpu().numpy().reshape(height, width, 4)
+                    changed = int(delta[0].item()) & 0xFFFFFFFF if k > 0 else None
+                    if on_pass is not None:
+                        on_pass(done, img, changed)
+                    k += 1
+                    if done >= cap:
+                        break
+                    if time_budget is not None and time.perf_counter() - t0 >= time_budget:
+                        break
+                    if until_changed_pixels is not None and changed is not None and changed <= until_changed_pixels:
+                        break
+            finally:
+                ctx.progressive_end()
+            self.last_linear = lin.cpu().numpy().reshape(height, width, 3)
+        self.last_samples = done
+        self.benchmark_data = {
+            "scene_name": "demo_scene",
+            "resolution": f"{width}x{height}",
+            "render_time_seconds": time.perf_counter() - t0,
+            "samples": done,
+            "max_depth": self.settings.max_depth,
+            "num_workers": self.settings.num_workers,
+            "timestamp": datetime.now(timezone.utc).isoformat(),
+            "features": list(self.FEATURES),
+            "passes": k,
+        }
+        return img
+
     def rank_seconds(self) -> list:
         """Device seconds of each rank's render launches in the last render (load balance)."""
         r = self._renderer()
@@ -732,6 +822,24 @@ class Context:
         _check(lib().rt_context_render_frames_async(self._h, width, height, ctypes.byref(settings), n, sd, rank, world,
                                                      layout, lp, rp, ctypes.c_void_p(stream)))
 
+    def progressive_begin(self, width, height, settings: Settings, rank: int = 0, world: int = 1,
+                          layout: int = RT_LAYOUT_IMAGE):
+        """rt_context_progressive_begin: start a progression of this frame; settings.samples is the cap."""
+        _check(lib().rt_context_progressive_begin(self._h, width, height, ctypes.byref(settings), rank, world, layout))
+
+    def progressive_add(self, nsamples: int, d_linear: int, d_rgba: int, stream: int = 0):
+        """rt_context_progressive_add_async: the next nsamples samples of every pixel, then the
+        image of the mean over all samples so far into d_linear / d_rgba (either may be 0)."""
+        _check(lib().rt_context_progressive_add_async(self._h, nsamples, ctypes.c_void_p(d_linear),
+                                                       ctypes.c_void_p(d_rgba), ctypes.c_void_p(stream)))
+
+    def progressive_samples(self) -> int:
+        """Samples per pixel the progression has rendered; -1: no progression."""
+        return int(lib().rt_context_progressive_samples(self._h))
+
+    def progressive_end(self):
+        _check(lib().rt_context_progressive_end(self._h))
+
     def set_partition(self, partition):
         """Render the tiles of `partition` (a Partition, or None: strided)."""
         self._partition = partition  # (copied by the library; kept for symmetry)
@@ -803,6 +911,13 @@ def render(scene: Scene, width: int, height: int, settings: Settings):
     _check(lib().rt_render(ctypes.byref(scene.view), width, height, ctypes.byref(settings), lin.ctypes.data,
                            rgba.ctypes.data, ctypes.byref(st)))
     return rgba, lin, st
+
+
+def rgba_delta_async(d_a: int, d_b: int, npix: int, d_out: int, stream: int = 0):
+    """rt_rgba_delta_async: two RGBA8 device images of npix pixels -> the device words d_out[0]
+    (pixels that differ) and d_out[1] (the largest byte difference); zeroes d_out first."""
+    _check(lib().rt_rgba_delta_async(ctypes.c_void_p(d_a), ctypes.c_void_p(d_b), npix, ctypes.c_void_p(d_out),
+                                     ctypes.c_void_p(stream)))
 
 
 def max_local_tiles(width: int, height: int, world: int) -> int:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 6  /* 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 7  /* 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -398,6 +398,36 @@ int rt_context_render_async(rt_context* ctx, int32_t width, int32_t height, cons
 int rt_context_render_frames_async(rt_context* ctx, int32_t width, int32_t height, const rt_settings* settings,
                                    int32_t nframes, const uint64_t* seeds, int32_t rank, int32_t world,
                                    int32_t layout, float* const* d_linear, uint8_t* const* d_rgba, void* hip_stream);
+
+/* Progressive rendering: one frame's samples rendered over
+ * several calls, with the image of the samples so far after each.  A context
+ * holds at most one progression.  begin: the frame (size, rank, world and
+ * layout as rt_context_render_async), with settings->samples the CAP, the
+ * most samples per pixel the progression may reach; it zeroes the
+ * progression's own per-pixel sums and starts over when the context already
+ * has one.  add_async: samples [done, done + nsamples) of every pixel of the
+ * rank's tiles, each pixel's sum continued in sample order, then the mean
+ * over done + nsamples samples written to d_linear / d_rgba (buffers as
+ * rt_context_render_async; either may be NULL) -- after adds totalling n
+ * samples the image is that of rt_context_render_async with samples = n,
+ * byte for byte.  nsamples < 1, done + nsamples > cap, no progression or an
+ * ended one: RT_E_INVALID, nothing changes.  samples: done so far, -1 without
+ * a progression.  end: frees the sums.  rt_context_set_scene, _set_tuning and
+ * _set_partition end a progression; ordinary renders between two adds do not
+ * disturb it.  An add counts in rt_context_stats.frames and .launches like a
+ * render; adds of equal nsamples share one work schedule. */
+int rt_context_progressive_begin(rt_context* ctx, int32_t width, int32_t height, const rt_settings* settings,
+                                 int32_t rank, int32_t world, int32_t layout);
+int rt_context_progressive_add_async(rt_context* ctx, int32_t nsamples, float* d_linear, uint8_t* d_rgba,
+                                     void* hip_stream);
+int64_t rt_context_progressive_samples(const rt_context* ctx);
+int rt_context_progressive_end(rt_context* ctx);
+/* How much two RGBA8 images of npix pixels (device pointers) differ, into the
+ * two device words d_out: [0] the pixels whose four bytes are not all equal,
+ * [1] the largest |a - b| over all bytes.  Zeroes d_out on the stream first.
+ * Exact and independent of order: a progression's stop criterion (how much
+ * the preview still moved in the last pass). */
+int rt_rgba_delta_async(const uint8_t* d_a, const uint8_t* d_b, size_t npix, uint32_t* d_out, void* hip_stream);
 
 /* What a context has done so far (diagnostics): work schedules built (a new
  * scene, frame, rank or settings key; a measured re-cut counts too),
