@@ -3,7 +3,7 @@
 //   raytracer <scene_file> <output_file> <width> <height>
 //             [--samples N] [--max-depth N] [--seed N] [--no-soft-shadows]
 //             [--no-recursive] [--devices N] [--watchdog SECONDS]
-//             [--sky default|white|sunset|night]
+//             [--sky default|white|sunset|night] [--camera reference|lookat]
 //             [--pass-samples N [--time-budget SECONDS] [--converge PIXELS]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
@@ -14,7 +14,8 @@
 // gains the published rays_per_second / pixels_per_second fields
 // (README.md:60-61), and the optional flags above (the Go CLI never calls
 // the renderer's setters, settings.go:3-25; --sky is the opt-in atmosphere,
-// include/rt_api.h RT_SKY_*).  --pass-samples N renders progressively on one
+// include/rt_api.h RT_SKY_*; --camera lookat honours the scene's lookAt, up
+// and fov instead of getRay's fixed -Z view, RT_CAMERA_*).  --pass-samples N renders progressively on one
 // device: N samples per pass up to the cap --samples, one
 // "Pass k: n samples[, c pixels changed]" line per pass, stopping early once
 // --time-budget SECONDS have passed or at most --converge PIXELS pixels of the
@@ -296,6 +297,14 @@ int main(int argc, char** argv) {
       else {
         fprintf(stderr, "unknown --sky %s\n", k.c_str());
         return 2;
+      }
+    } else if (a == "--camera") {  // reference (default): getRay's fixed -Z view; lookat: the scene's own camera
+      const std::string k = need("--camera");
+      if (k == "reference") st.camera = RT_CAMERA_REFERENCE;
+      else if (k == "lookat") st.camera = RT_CAMERA_LOOKAT;
+      else {
+        fprintf(stderr, "unknown --camera %s (reference or lookat)\n", k.c_str());
+        return 1;
       }
     } else {
       args.push_back(a);

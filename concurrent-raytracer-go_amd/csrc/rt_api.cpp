@@ -89,7 +89,18 @@ static int validate_settings(const rt_settings* st, int32_t w, int32_t h) {
     set_error("sky must be one of RT_SKY_*");
     return RT_E_INVALID;
   }
+  if (st->camera != RT_CAMERA_REFERENCE && st->camera != RT_CAMERA_LOOKAT) {
+    set_error("camera must be RT_CAMERA_REFERENCE or RT_CAMERA_LOOKAT");
+    return RT_E_INVALID;
+  }
   return RT_OK;
+}
+
+// The scene's camera under st's camera model (after validate_settings): a
+// degenerate look-at camera is RT_E_INVALID at every render entry point.
+static int validate_camera(const rt_camera& cam, const rt_settings* st, int32_t w, int32_t h) {
+  CamFrame cf;
+  return camera_frame(cam, st->camera, w, h, &cf);
 }
 
 }  // namespace rtgo
@@ -374,7 +385,22 @@ int rt_debug_xlane_faults(int32_t device, int32_t reset, uint64_t* out) {
 int rt_validate(const rt_scene* scene, int32_t w, int32_t h, const rt_settings* st) {
   int rc = validate_scene(scene);
   if (rc) return rc;
-  return validate_settings(st, w, h);
+  rc = validate_settings(st, w, h);
+  if (rc) return rc;
+  CamFrame cf;  // (a degenerate look-at camera: RT_E_INVALID with its message)
+  return camera_frame(scene->camera, st->camera, w, h, &cf);
+}
+
+int rt_camera_frame(const rt_camera* cam, int32_t model, int32_t w, int32_t h, double out[12]) {
+  if (!cam || !out) {
+    set_error("camera or out is NULL");
+    return RT_E_INVALID;
+  }
+  CamFrame cf;
+  const int rc = camera_frame(*cam, model, w, h, &cf);
+  if (rc) return rc;
+  memcpy(out, cf.o, 12 * sizeof(double));  // o, ll, h, v are contiguous
+  return RT_OK;
 }
 
 const char* rt_last_error(void) { return g_last_error.c_str(); }
@@ -643,8 +669,8 @@ static void base_params(const rt_context* c, int w, int h, const rt_settings* st
   p.jump = c->d_jump;
   p.sky = st->sky != RT_SKY_NONE ? c->d_sky + (st->sky - 1) : nullptr;
   p.dbg = c->dbg;
-  memcpy(p.cam, f.cam_pos, sizeof p.cam);
-  p.aspect = f.aspect;
+  // (the entry points have validated st and the camera: validate_camera)
+  (void)camera_frame(f.camera, st->camera, w, h, &p.cf);
   p.seed_key = rt_rng_seed_key(st->seed);
   p.ns = (int32_t)f.spheres.size();
   p.nt = (int32_t)f.tris.size();
@@ -725,15 +751,13 @@ static int setup_tail(rt_context* c, KParams* p, hipStream_t s) {
 static SchedParams sched_params(rt_context* c, const KParams& p, const rt_settings* st, const std::vector<int32_t>& tiles,
                                 const int32_t* d_tiles, bool masks, bool frustum, double block_work, int bigP,
                                 void* scratch, unsigned long long* d_masks, float* d_cost) {
-  const FlatScene& f = c->flat;
   const rt_tuning& tn = c->tun;
   SchedParams sp;
   memset(&sp, 0, sizeof sp);
   sched_layout(scratch, (int)tiles.size(), &sp);
   sp.spheres = c->d_spheres;
   sp.tris = c->d_tris;
-  memcpy(sp.cam, f.cam_pos, sizeof sp.cam);
-  sp.vw = 2.0 * f.aspect;
+  sp.cf = p.cf;
   sp.W = p.W;
   sp.H = p.H;
   sp.rank = p.rank;
@@ -870,7 +894,8 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
   const int64_t key[14] = {(int64_t)c->scene_gen, w, h, rank, world, st->samples, st->max_depth,
                            st->recursive_reflections, st->soft_shadows, bigP, (int64_t)(block_work * 16),
                            (pilot ? 1 + tn.pilot_depth : 0) | (int64_t)tn.split_samples << 16,
-                           (frustum ? 1 : 0) | (sky ? 2 : 0) | (tn.measure ? 4 : 0) | (want_live ? 8 : 0) | (int64_t)tn.split_depth << 8,
+                           (frustum ? 1 : 0) | (sky ? 2 : 0) | (tn.measure ? 4 : 0) | (want_live ? 8 : 0) | (st->camera ? 16 : 0) |
+                               (int64_t)tn.split_depth << 8,
                            part ? (int64_t)c->part->id : 0};
   const bool masks = masks_apply(f);
   const bool new_key = memcmp(key, c->order_key, sizeof key) != 0;
@@ -891,9 +916,9 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
     c->d_masks = nullptr;
     if (local > 0) {
       // per-tile inputs (host): primary-ray candidate masks, projected-primitive counts
-      if (masks) tile_primary_masks(f, w, h, tiles, &c->masks_host);
+      if (masks) tile_primary_masks(f, p->cf, w, h, tiles, &c->masks_host);
       std::vector<float> cost;
-      tile_cost(f, w, h, tiles, &cost);
+      tile_cost(f, p->cf, w, h, tiles, &cost);
       const size_t scratch = sched_scratch_bytes(local);
       const size_t mbytes = c->masks_host.size() * sizeof(unsigned long long), cbytes = cost.size() * sizeof(float);
       const size_t inputs = mbytes + cbytes;
@@ -1166,8 +1191,7 @@ static int render_wavefront(rt_context* c, const KParams& kp, const rt_settings*
   p.shard_cap = shard_cap;
   p.hard_cap = (int64_t)qcap;
   p.soft_cap = (int64_t)qcap * 16;
-  memcpy(p.cam, kp.cam, sizeof p.cam);
-  p.aspect = kp.aspect;
+  p.cf = kp.cf;
   p.seed_key = kp.seed_key;
   p.ctl = c->wf_ctl;
   p.counts = kp.counts;
@@ -1340,6 +1364,8 @@ static int render_one(rt_context* c, int32_t w, int32_t h, const rt_settings* st
     return RT_E_INVALID;
   }
   int rc = validate_settings(st, w, h);
+  if (rc) return rc;
+  rc = validate_camera(c->flat.camera, st, w, h);
   if (rc) return rc;
   if (world < 1 || rank < 0 || rank >= world) {
     set_error("invalid rank/world");
@@ -1585,6 +1611,8 @@ static int partition_balanced_impl(rt_context* c, int32_t w, int32_t h, const rt
   *out = nullptr;
   int rc = validate_settings(st, w, h);
   if (rc) return rc;
+  rc = validate_camera(c->flat.camera, st, w, h);
+  if (rc) return rc;
   if (world < 1 || world > 65536) {
     set_error("rt_partition_balanced: world must be in [1, 65536]");
     return RT_E_INVALID;
@@ -1615,9 +1643,9 @@ static int partition_balanced_impl(rt_context* c, int32_t w, int32_t h, const rt
   const bool masks = masks_apply(f);
   const bool frustum = tn.frustum != 0 && st->sky == RT_SKY_NONE;
   std::vector<unsigned long long> mh;
-  if (masks) tile_primary_masks(f, w, h, tiles, &mh);
+  if (masks) tile_primary_masks(f, p.cf, w, h, tiles, &mh);
   std::vector<float> cost;
-  tile_cost(f, w, h, tiles, &cost);
+  tile_cost(f, p.cf, w, h, tiles, &cost);
   auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t npx = (size_t)ntiles * 1024;
   const size_t o_in = al(sched_scratch_bytes(ntiles));
@@ -1720,6 +1748,8 @@ int rt_context_render_frames_async(rt_context* c, int32_t w, int32_t h, const rt
   }
   int rc = validate_settings(st, w, h);
   if (rc) return rc;
+  rc = validate_camera(c->flat.camera, st, w, h);
+  if (rc) return rc;
   if (world < 1 || rank < 0 || rank >= world) {
     set_error("invalid rank/world");
     return RT_E_INVALID;
@@ -1795,6 +1825,8 @@ int rt_context_progressive_begin(rt_context* c, int32_t w, int32_t h, const rt_s
     return RT_E_INVALID;
   }
   int rc = validate_settings(st, w, h);
+  if (rc) return rc;
+  rc = validate_camera(c->flat.camera, st, w, h);
   if (rc) return rc;
   if (world < 1 || rank < 0 || rank >= world) {
     set_error("invalid rank/world");

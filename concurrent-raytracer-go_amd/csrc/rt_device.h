@@ -584,9 +584,16 @@ __device__ __forceinline__ Scat scatter(const DMat* __restrict__ m, d3 d, d3 N, 
 
 // ------------------------------------------------------------ camera
 // Launch-uniform inputs of the camera rays (getRay, renderer.go:377-390).
+// The frame (CamFrame: origin, lower-left corner, horizontal, vertical) comes
+// from the kernel arguments, twelve launch-uniform doubles (SGPRs).  The
+// reference model reads vw = horizontal.x, the corner and the origin only,
+// and CamK holds just those; the look-at model (lookat != 0, launch-uniform)
+// loads the other five from the arguments inside its branch, so the
+// reference path keeps no register for them.
 struct CamK {
   uint64_t key;
   uint32_t W;
+  int32_t lookat;
   double dW, dH, vw, llcx, llcy, llcz, ox, oy, oz;
   double rW, rH;  // refined reciprocals of dW, dH (div_by)
 };
@@ -609,18 +616,33 @@ __device__ __forceinline__ double div_by(double n, double d, double r) {
   const double q = n * r;
   return __builtin_fma(__builtin_fma(-d, q, n), r, q);
 }
-template <bool kCount>
-__device__ __forceinline__ void camera_ray_c(const CamK& ck, int x, int y, int s, rt_rng& rng, d3& o, d3& d,
-                                             Counters& c) {
+// (Frame: CamFrame in whatever address space the caller holds its arguments)
+template <bool kCount, class Frame>
+__device__ __forceinline__ void camera_ray_c(const CamK& ck, const Frame& f, int x, int y, int s, rt_rng& rng, d3& o,
+                                             d3& d, Counters& c) {
   rt_rng_init(&rng, ck.key, (uint32_t)y * ck.W + (uint32_t)x, (uint32_t)s);
   const double u = div_by((double)x + draw<kCount>(rng, c), ck.dW, ck.rW);
   const double v = div_by((double)y + draw<kCount>(rng, c), ck.dH, ck.rH);
   o = mk(ck.ox, ck.oy, ck.oz);
-  d = mk(((ck.llcx + ck.vw * u) + 0.0) - o.x, ((ck.llcy + 0.0) + 2.0 * v) - o.y, ((ck.llcz + 0.0) + 0.0) - o.z);
+  if (!ck.lookat) {  // getRay: horizontal = (vw, 0, 0), vertical = (0, 2, 0)
+    d = mk(((ck.llcx + ck.vw * u) + 0.0) - o.x, ((ck.llcy + 0.0) + 2.0 * v) - o.y, ((ck.llcz + 0.0) + 0.0) - o.z);
+  } else {  // ((lowerLeft + horizontal * u) + vertical * v) - origin, not normalised
+    // (one component at a time, its two terms moved to VGPRs: the scalar
+    // loads then need one register pair at a time in an SGPR-bound kernel)
+    const double dx = ((ck.llcx + ck.vw * u) + inv(f.v[0]) * v) - o.x;
+    const double dy = ((ck.llcy + inv(f.h[1]) * u) + inv(f.v[1]) * v) - o.y;
+    const double dz = ((ck.llcz + inv(f.h[2]) * u) + inv(f.v[2]) * v) - o.z;
+    d = mk(dx, dy, dz);
+  }
 }
 
-__device__ __forceinline__ CamK make_cam(uint64_t seed_key, int W, int H, double aspect, double cx, double cy,
-                                         double cz) {
+// `f` lives in the kernel arguments (camera_frame, rt_api.cpp).  The
+// reference model keeps forming its corner here from the origin and vw, the
+// three operations the kernels have always executed (the host's frame holds
+// the same bits): loading it instead changed the register allocation of the
+// SGPR-bound block kernels.
+template <class Frame>
+__device__ __forceinline__ CamK make_cam(uint64_t seed_key, int W, int H, const Frame& f) {
   CamK r;
   r.key = seed_key;
   r.W = (uint32_t)W;
@@ -628,14 +650,21 @@ __device__ __forceinline__ CamK make_cam(uint64_t seed_key, int W, int H, double
   r.dH = (double)H;
   r.rW = refined_rcp(r.dW);
   r.rH = refined_rcp(r.dH);
-  // lowerLeftCorner = origin - horizontal/2 - vertical/2 - (0,0,focal)
-  r.vw = 2.0 * aspect;
-  r.llcx = cx - r.vw / 2;
-  r.llcy = cy - 1.0;
-  r.llcz = cz - 1.0;
-  r.ox = cx;
-  r.oy = cy;
-  r.oz = cz;
+  r.lookat = f.model;
+  r.vw = f.h[0];
+  r.ox = f.o[0];
+  r.oy = f.o[1];
+  r.oz = f.o[2];
+  if (!r.lookat) {
+    // lowerLeftCorner = origin - horizontal/2 - vertical/2 - (0,0,focal)
+    r.llcx = r.ox - r.vw / 2;
+    r.llcy = r.oy - 1.0;
+    r.llcz = r.oz - 1.0;
+  } else {
+    r.llcx = f.ll[0];
+    r.llcy = f.ll[1];
+    r.llcz = f.ll[2];
+  }
   return r;
 }
 

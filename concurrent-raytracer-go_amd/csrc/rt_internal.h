@@ -48,8 +48,21 @@ struct FlatScene {
   double q0[3] = {0, 0, 0}, qd[3] = {1, 1, 1};  // its grid: coordinate = q0 + q * qd
   double cam_pos[3] = {0, 0, 0};
   double aspect = 0;
+  rt_camera camera{};         // the scene's camera as given (the look-at model reads all of it)
   int32_t objects = 0;        // len(hittables)
 };
+
+// The viewport frame of a launch's camera rays (rt_camera_frame,
+// include/rt_api.h): ray(u, v) = ((ll + h * u) + v * v) - o per component.
+// model RT_CAMERA_REFERENCE: h = (2 * aspect, 0, 0), v = (0, 2, 0) and the
+// kernels evaluate getRay's own expressions (renderer.go:377-390).
+struct CamFrame {
+  double o[3], ll[3], h[3], v[3];
+  int32_t model, _pad;
+};
+// Fills out->o .. out->v and out->model; RT_E_INVALID (message set) for an
+// unknown model or a degenerate look-at camera.
+int camera_frame(const rt_camera& cam, int32_t model, int32_t w, int32_t h, CamFrame* out);
 
 // The AtmosphereConfig presets of RT_SKY_DEFAULT .. RT_SKY_NIGHT
 // (internal/atmosphere/atmosphere.go:28-98), index sky - 1.
@@ -67,6 +80,9 @@ void build_sphere_bvh(FlatScene* fs, int bins, int leaf);
 void strided_tiles(int32_t W, int32_t H, int32_t rank, int32_t world, std::vector<int32_t>* tiles);
 // Per local tile: primitives whose projected bounds overlap it (the work
 // estimate of a schedule without a pilot render).
+void tile_cost(const FlatScene& fs, const CamFrame& cf, int32_t W, int32_t H, const std::vector<int32_t>& tiles,
+               std::vector<float>* local_cost);
+// (the reference camera of fs.camera: the schedule inputs as they were before the frame)
 void tile_cost(const FlatScene& fs, int32_t W, int32_t H, const std::vector<int32_t>& tiles,
                std::vector<float>* local_cost);
 constexpr int32_t kBlockBlack = 1;  // block flag (8th int): black tile, nothing to trace
@@ -74,6 +90,8 @@ constexpr int kBlockInts = 16;      // ints per work block record (KParams::bloc
 // Primary-ray candidate masks per local tile (2 x u64: spheres, triangles;
 // scenes with <= 64 of each): bit i set unless primitive i's bounding sphere
 // provably misses the cone of the tile's camera rays.
+void tile_primary_masks(const FlatScene& fs, const CamFrame& cf, int32_t W, int32_t H,
+                        const std::vector<int32_t>& tiles, std::vector<unsigned long long>* masks);
 void tile_primary_masks(const FlatScene& fs, int32_t W, int32_t H, const std::vector<int32_t>& tiles,
                         std::vector<unsigned long long>* masks);
 
@@ -81,8 +99,7 @@ void tile_primary_masks(const FlatScene& fs, int32_t W, int32_t H, const std::ve
 struct SchedParams {
   const DSphere* spheres;
   const DTri* tris;
-  double cam[3];
-  double vw;                   // viewport width 2 * aspect (getRay, renderer.go:377-390)
+  CamFrame cf;                 // the camera rays' frame (getRay, renderer.go:377-390, or the look-at model)
   int32_t W, H, rank, world, tiles_x, ntiles, local;
   int32_t spp, big_pixels, frustum;
   int32_t split_samples;       // samples per sub-block of a split pixel (<= 64: one path per lane)
@@ -229,8 +246,7 @@ struct KParams {
   int32_t stage_bytes;         // bytes to stage (multiple of 16); 0 = read the scene from global memory
   int32_t stack_off;           // byte offset of the BVH stacks in dynamic LDS
   int32_t stack_depth;         // entries per lane of a BVH stack (the tree's depth)
-  double cam[3];
-  double aspect;
+  CamFrame cf;               // the camera rays' frame (rt_camera_frame)
   uint64_t seed_key;
   int32_t ns, nt, nl, use_bvh, nb;
   int32_t W, H;
@@ -407,8 +423,7 @@ struct WfParams {
   int32_t dry;               // 1: every sample of the chunk has started (no regen work left)
   int64_t hard_cap, soft_cap;  // queue entries per shard
   uint32_t lp0;              // first local pixel of the chunk (local tile * 1024 + pixel in tile)
-  double cam[3];
-  double aspect;
+  CamFrame cf;               // the camera rays' frame (rt_camera_frame)
   uint64_t seed_key;
   WfPaths cur, next;
   WfCtl* ctl;

@@ -620,11 +620,11 @@ __device__ __forceinline__ Hot hot() {
 // the launch-uniform inputs; phase 1 loads it once per block (SGPRs), the
 // shading loop rebuilds it from the kernarg segment where it needs it.
 __device__ __forceinline__ CamK cam_k(KArg k) {
-  return make_cam(k->frame_key[frame_of(k)], k->W, k->H, k->aspect, k->cam[0], k->cam[1], k->cam[2]);
+  return make_cam(k->frame_key[frame_of(k)], k->W, k->H, k->cf);
 }
 template <bool kCount>
 __device__ __forceinline__ void camera_ray(KArg k, int x, int y, int s, rt_rng& rng, d3& o, d3& d, Counters& c) {
-  camera_ray_c<kCount>(cam_k(k), x, y, s, rng, o, d, c);
+  camera_ray_c<kCount>(cam_k(k), k->cf, x, y, s, rng, o, d, c);
 }
 
 // ------------------------------------------------------------ solo paths
@@ -1526,7 +1526,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
         cnt<kCount>(cs, C_CAM);
         rt_rng rng;
         d3 o, d;
-        camera_ray_c<kCount>(ck, x, y, sbase + s, rng, o, d, cs);
+        camera_ray_c<kCount>(ck, k->cf, x, y, sbase + s, rng, o, d, cs);
         if (!trace) return;
         cnt<kCount>(cs, C_BOUNCE);
         // hit or miss is all this phase needs: an any-hit query over
@@ -1777,7 +1777,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               // kernel's refill below builds them (kBase: the frame's sample
               // sample_base + s, a progression's add)
               const unsigned fs = kBase ? (unsigned)sk->k.sample_base + s : s;
-              camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, sk->k.aspect, sk->k.cam[0], sk->k.cam[1], sk->k.cam[2]),
+              camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, sk->k.cf), sk->k.cf,
                                   it.x, it.y, (int)fs, rng, o, d, nc);
               skey[lane_now()] = rt_soft_key(fkey, (uint32_t)it.y * (uint32_t)sk->k.W + (uint32_t)it.x, (uint32_t)fs);
               entry = (int)((fl * spp + s) * nlive + i);

@@ -279,7 +279,7 @@ int renderer_partition(rt_renderer* r, const rt_scene* scene, int32_t w, int32_t
     return RT_OK;
   }
   const std::vector<int64_t> key = {(int64_t)r->scene_gen, w, h, n, st->samples, st->max_depth,
-                                    st->recursive_reflections, st->soft_shadows, st->sky};
+                                    st->recursive_reflections, st->soft_shadows, st->sky, st->camera};
   if (r->part && key == r->part_key) return RT_OK;
   rt_partition* p = nullptr;
   int rc = partition_balanced(r->ranks[0].ctx, w, h, st, n, kRendererPartitionSpp, &p);

@@ -67,8 +67,30 @@ __device__ bool cone_meets_sphere(const double* c, double r, const double* apex,
 
 // The cone around the camera rays of pixel (x, y): getRay direction
 // (vw*(u-1/2), 2*(v-1/2), -1) with u in [x/W, (x+1)/W], v in [y/H, (y+1)/H]
-// (renderer.go:155-156,377-390).
-__device__ void pixel_cone(double vw, int W, int H, int x, int y, double* axis, double* cmin, double* smax) {
+// (renderer.go:155-156,377-390).  Look-at model: the four corner directions
+// (ll + h u + v v) - o of the same rectangle; the axis is the normalised
+// centre direction and the half-angle that of the widest corner (the set of
+// directions within an angle of the axis cuts the image plane in a convex
+// set whatever the plane's orientation).  The apex is cf.o in both.
+__device__ void pixel_cone(const CamFrame& cf, int W, int H, int x, int y, double* axis, double* cmin, double* smax) {
+  if (cf.model != RT_CAMERA_REFERENCE) {
+    const double u[2] = {(double)x / W, (double)(x + 1) / W}, v[2] = {(double)y / H, (double)(y + 1) / H};
+    double cd[4][3];
+    for (int k = 0; k < 4; ++k)
+      for (int a = 0; a < 3; ++a) cd[k][a] = ((cf.ll[a] + cf.h[a] * u[k & 1]) + cf.v[a] * v[k >> 1]) - cf.o[a];
+    for (int a = 0; a < 3; ++a) axis[a] = 0.25 * ((cd[0][a] + cd[1][a]) + (cd[2][a] + cd[3][a]));
+    const double al = sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    for (int a = 0; a < 3; ++a) axis[a] /= al;
+    double c = 1.0;
+    for (int k = 0; k < 4; ++k) {
+      const double cl = sqrt(cd[k][0] * cd[k][0] + cd[k][1] * cd[k][1] + cd[k][2] * cd[k][2]);
+      c = fmin(c, (axis[0] * cd[k][0] + axis[1] * cd[k][1] + axis[2] * cd[k][2]) / cl);
+    }
+    *cmin = c;
+    *smax = sqrt(fmax(0.0, 1.0 - c * c));
+    return;
+  }
+  const double vw = cf.h[0];
   const double dx0 = vw * ((double)x / W - 0.5), dx1 = vw * ((double)(x + 1) / W - 0.5);
   const double dy0 = 2.0 * ((double)y / H - 0.5), dy1 = 2.0 * ((double)(y + 1) / H - 0.5);
   axis[0] = 0.5 * (dx0 + dx1);
@@ -106,14 +128,14 @@ __global__ __launch_bounds__(64) void sched_pixels(const SchedParams p) {
     const int x = (t % p.tiles_x) * 32 + (q & 31), y = (t / p.tiles_x) * 32 + (q >> 5);
     if (t < p.ntiles && (ts | tt) && x < p.W && y < p.H) {
       double axis[3], cmin, smax;
-      pixel_cone(p.vw, p.W, p.H, x, y, axis, &cmin, &smax);
+      pixel_cone(p.cf, p.W, p.H, x, y, axis, &cmin, &smax);
       for (unsigned long long b = ts; b; b &= b - 1) {
         const int i = __builtin_ctzll(b);
-        if (cone_meets_sphere(p.spheres[i].c, p.spheres[i].r, p.cam, axis, cmin, smax)) ms |= 1ull << i;
+        if (cone_meets_sphere(p.spheres[i].c, p.spheres[i].r, p.cf.o, axis, cmin, smax)) ms |= 1ull << i;
       }
       for (unsigned long long b = tt; b; b &= b - 1) {
         const int i = __builtin_ctzll(b);
-        if (cone_meets_sphere(p.tris[i].bc, p.tris[i].br, p.cam, axis, cmin, smax)) mt |= 1ull << i;
+        if (cone_meets_sphere(p.tris[i].bc, p.tris[i].br, p.cf.o, axis, cmin, smax)) mt |= 1ull << i;
       }
     }
     p.pixmask[((size_t)lt * 1024 + q) * 2] = ms;

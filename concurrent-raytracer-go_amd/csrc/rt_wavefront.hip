@@ -1610,10 +1610,10 @@ __global__ __launch_bounds__(kWfBlock) void wf_regen(const WfParams p) {
         p.next.sid[slot] = kDeadSid;
       } else {
         cnt<kCount>(c, C_CAM);
-        const CamK ck = make_cam(p.seed_key, p.W, p.H, p.aspect, p.cam[0], p.cam[1], p.cam[2]);
+        const CamK ck = make_cam(p.seed_key, p.W, p.H, p.cf);
         rt_rng rng;
         d3 o, d;
-        camera_ray_c<kCount>(ck, x, y, p.sample_base + smp, rng, o, d, c);
+        camera_ray_c<kCount>(ck, p.cf, x, y, p.sample_base + smp, rng, o, d, c);
         store_path(p.next, slot, o, d, mk(1, 1, 1), mk(0, 0, 0), rng.x, sid, 0);
       }
     }

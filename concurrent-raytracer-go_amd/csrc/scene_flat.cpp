@@ -264,7 +264,97 @@ void flatten_scene(const rt_scene& s, FlatScene* fs) {
   }
   put(fs->cam_pos, arr(s.camera.position));
   fs->aspect = s.camera.aspect_ratio;
+  fs->camera = s.camera;
   fs->objects = s.num_objects;
+}
+
+// Go's Vec3 methods (internal/math/vector.go) on the host, for the frame
+namespace {
+struct V3 {
+  double x, y, z;
+};
+V3 vsub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+V3 vmuls(V3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
+V3 vdivs(V3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
+V3 vcross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+double vlen(V3 a) { return sqrt(a.x * a.x + a.y * a.y + a.z * a.z); }
+V3 varr(const double* p) { return {p[0], p[1], p[2]}; }
+void vput(double* p, V3 a) {
+  p[0] = a.x;
+  p[1] = a.y;
+  p[2] = a.z;
+}
+}  // namespace
+
+// rt_camera_frame (include/rt_api.h states the definition and the order)
+int camera_frame(const rt_camera& cam, int32_t model, int32_t w, int32_t h, CamFrame* out) {
+  memset(out, 0, sizeof *out);
+  const V3 origin = varr(cam.position);
+  V3 horizontal, vertical, ll;
+  if (model == RT_CAMERA_REFERENCE) {
+    // getRay (renderer.go:377-390): aspect and position only
+    horizontal = {2.0 * cam.aspect_ratio, 0, 0};
+    vertical = {0, 2.0, 0};
+    ll = vsub(vsub(vsub(origin, vdivs(horizontal, 2)), vdivs(vertical, 2)), V3{0, 0, 1.0});
+  } else if (model == RT_CAMERA_LOOKAT) {
+    if (w <= 0 || h <= 0) {
+      set_error("camera frame: invalid image size " + std::to_string(w) + "x" + std::to_string(h));
+      return RT_E_INVALID;
+    }
+    const double fields[11] = {cam.position[0], cam.position[1], cam.position[2], cam.look_at[0],
+                               cam.look_at[1],  cam.look_at[2],  cam.up[0],       cam.up[1],
+                               cam.up[2],       cam.fov,         cam.aspect_ratio};
+    for (double v : fields)
+      if (!std::isfinite(v)) {
+        set_error("look-at camera: position, lookAt, up, fov and aspectRatio must be finite");
+        return RT_E_INVALID;
+      }
+    if (!(cam.fov > 0 && cam.fov < 180)) {
+      set_error("look-at camera: fov must be in (0, 180) degrees");
+      return RT_E_INVALID;
+    }
+    if (cam.aspect_ratio < 0) {
+      set_error("look-at camera: aspectRatio must not be negative (0: width / height)");
+      return RT_E_INVALID;
+    }
+    const V3 back = vsub(origin, varr(cam.look_at));
+    const double bl = vlen(back);
+    if (bl == 0) {
+      set_error("look-at camera: position equals lookAt");
+      return RT_E_INVALID;
+    }
+    const V3 wv = vdivs(back, bl);  // Vec3.Normalize
+    const V3 side = vcross(varr(cam.up), wv);
+    const double sl = vlen(side);
+    if (sl == 0) {
+      set_error("look-at camera: up is zero or parallel to the viewing direction");
+      return RT_E_INVALID;
+    }
+    const V3 U = vdivs(side, sl);
+    const V3 V = vcross(wv, U);
+    // exactly 1 at 90 degrees, the reference's viewport (tan(pi/4) rounds below 1)
+    const double hh = cam.fov == 90 ? 1.0 : tan(cam.fov * (M_PI / 360));
+    const double a = cam.aspect_ratio != 0 ? cam.aspect_ratio : (double)w / h;
+    const double vh = 2.0 * hh, vw = vh * a;
+    horizontal = vmuls(U, vw);
+    vertical = vmuls(V, vh);
+    ll = vsub(vsub(vsub(origin, vdivs(horizontal, 2)), vdivs(vertical, 2)), wv);
+    const double fr[9] = {horizontal.x, horizontal.y, horizontal.z, vertical.x, vertical.y, vertical.z, ll.x, ll.y, ll.z};
+    for (double v : fr)
+      if (!std::isfinite(v)) {
+        set_error("look-at camera: the viewport frame overflows binary64");
+        return RT_E_INVALID;
+      }
+  } else {
+    set_error("camera must be RT_CAMERA_REFERENCE or RT_CAMERA_LOOKAT");
+    return RT_E_INVALID;
+  }
+  vput(out->o, origin);
+  vput(out->ll, ll);
+  vput(out->h, horizontal);
+  vput(out->v, vertical);
+  out->model = model;
+  return RT_OK;
 }
 
 }  // namespace rtgo
@@ -284,6 +374,7 @@ void rt_settings_default(rt_settings* s) {
   s->num_workers = 1;
   s->num_devices = 1;
   s->seed = 1;
+  s->camera = RT_CAMERA_REFERENCE;  // getRay's fixed -Z view; the scene's lookAt / up / fov are opt-in
 }
 
 void rt_tuning_default(rt_tuning* t) {

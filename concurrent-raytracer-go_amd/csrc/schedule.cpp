@@ -24,14 +24,36 @@ void strided_tiles(int32_t W, int32_t H, int32_t rank, int32_t world, std::vecto
   for (int t = rank; t < ntiles; t += world) tiles->push_back(t);
 }
 
-void tile_cost(const FlatScene& fs, int32_t W, int32_t H, const std::vector<int32_t>& tiles,
+// Look-at model: the same projection in camera coordinates.  The frame's
+// horizontal = U * (2 a h), vertical = V * (2 h) and lower_left give back the
+// unit axes U, V, w and the half-extents a h and h; a centre is (dot U, dot V,
+// dot w) of its offset from the origin, and the camera looks down -w.
+void tile_cost(const FlatScene& fs, const CamFrame& cf, int32_t W, int32_t H, const std::vector<int32_t>& tiles,
                std::vector<float>* local_cost) {
   const int tiles_x = (W + 31) / 32, tiles_y = (H + 31) / 32, ntiles = tiles_x * tiles_y;
   std::vector<float> cost(ntiles, 0.0f);
-  const double vw = 2.0 * fs.aspect;
+  const bool lookat = cf.model != RT_CAMERA_REFERENCE;
+  double U[3] = {1, 0, 0}, V[3] = {0, 1, 0}, Wv[3] = {0, 0, 1}, vh = 2.0;
+  double vw = cf.h[0];
+  if (lookat) {
+    vw = sqrt(cf.h[0] * cf.h[0] + cf.h[1] * cf.h[1] + cf.h[2] * cf.h[2]);
+    vh = sqrt(cf.v[0] * cf.v[0] + cf.v[1] * cf.v[1] + cf.v[2] * cf.v[2]);
+    for (int k = 0; k < 3; ++k) {
+      U[k] = cf.h[k] / vw;
+      V[k] = cf.v[k] / vh;
+      // w = origin - horizontal/2 - vertical/2 - lower_left
+      Wv[k] = cf.o[k] - cf.h[k] / 2 - cf.v[k] / 2 - cf.ll[k];
+    }
+  }
   auto add_sphere = [&](const double* c, double r) {
     const double R = fabs(r);
-    const double cx = c[0] - fs.cam_pos[0], cy = c[1] - fs.cam_pos[1], cz = c[2] - fs.cam_pos[2];
+    double cx = c[0] - cf.o[0], cy = c[1] - cf.o[1], cz = c[2] - cf.o[2];
+    if (lookat) {
+      const double ox = cx, oy = cy, oz = cz;
+      cx = ox * U[0] + oy * U[1] + oz * U[2];
+      cy = ox * V[0] + oy * V[1] + oz * V[2];
+      cz = ox * Wv[0] + oy * Wv[1] + oz * Wv[2];
+    }
     if (cz - R >= 0) return;  // entirely behind the camera: no camera ray reaches it
     if (cz + R > -1e-9 || !(fabs(vw) > 0)) {  // straddles the camera plane: everywhere
       for (auto& v : cost) v += 1.0f;
@@ -41,7 +63,7 @@ void tile_cost(const FlatScene& fs, int32_t W, int32_t H, const std::vector<int3
     double u0 = INFINITY, u1 = -INFINITY, v0 = INFINITY, v1 = -INFINITY;
     for (int k = 0; k < 8; ++k) {
       const double qx = cx + ((k & 1) ? R : -R), qy = cy + ((k & 2) ? R : -R), qz = cz + ((k & 4) ? R : -R);
-      const double u = 0.5 + qx / (-qz * vw), v = 0.5 + qy / (-qz * 2.0);
+      const double u = 0.5 + qx / (-qz * vw), v = 0.5 + qy / (-qz * vh);
       u0 = fmin(u0, u);
       u1 = fmax(u1, u);
       v0 = fmin(v0, v);
@@ -79,9 +101,29 @@ static bool cone_meets_sphere(const double c[3], double r, const double apex[3],
 // The cone around the camera rays of the image rectangle [x0, x1) x [y0, y1)
 // (pixels): getRay direction (vw*(u-1/2), 2*(v-1/2), -1) with u in
 // [x0/W, x1/W], v in [y0/H, y1/H] (renderer.go:155-156,377-390): unit axis
-// and the cosine / sine of its half-angle.
-static void rect_cone(double vw, int32_t W, int32_t H, int x0, int x1, int y0, int y1, double axis[3], double* cmin,
-                      double* smax) {
+// and the cosine / sine of its half-angle.  Look-at model: the four corner
+// directions from the frame, the normalised centre direction as the axis and
+// the widest corner's angle (pixel_cone of rt_schedule.hip, for a rectangle).
+static void rect_cone(const CamFrame& cf, int32_t W, int32_t H, int x0, int x1, int y0, int y1, double axis[3],
+                      double* cmin, double* smax) {
+  if (cf.model != RT_CAMERA_REFERENCE) {
+    const double u[2] = {(double)x0 / W, (double)x1 / W}, v[2] = {(double)y0 / H, (double)y1 / H};
+    double cd[4][3];
+    for (int k = 0; k < 4; ++k)
+      for (int a = 0; a < 3; ++a) cd[k][a] = ((cf.ll[a] + cf.h[a] * u[k & 1]) + cf.v[a] * v[k >> 1]) - cf.o[a];
+    for (int a = 0; a < 3; ++a) axis[a] = 0.25 * ((cd[0][a] + cd[1][a]) + (cd[2][a] + cd[3][a]));
+    const double al = sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    for (int a = 0; a < 3; ++a) axis[a] /= al;
+    double c = 1.0;
+    for (int k = 0; k < 4; ++k) {
+      const double cl = sqrt(cd[k][0] * cd[k][0] + cd[k][1] * cd[k][1] + cd[k][2] * cd[k][2]);
+      c = fmin(c, (axis[0] * cd[k][0] + axis[1] * cd[k][1] + axis[2] * cd[k][2]) / cl);
+    }
+    *cmin = c;
+    *smax = sqrt(fmax(0.0, 1.0 - c * c));
+    return;
+  }
+  const double vw = cf.h[0];
   const double dx0 = vw * ((double)x0 / W - 0.5), dx1 = vw * ((double)x1 / W - 0.5);
   const double dy0 = 2.0 * ((double)y0 / H - 0.5), dy1 = 2.0 * ((double)y1 / H - 0.5);
   axis[0] = 0.5 * (dx0 + dx1);
@@ -101,38 +143,52 @@ static void rect_cone(double vw, int32_t W, int32_t H, int x0, int x1, int y0, i
 
 // candidates among `cand` (bit i: sphere / triangle i) whose bounding sphere
 // meets the cone
-static void cone_masks(const FlatScene& fs, const double axis[3], double cmin, double smax, unsigned long long cand_s,
+static void cone_masks(const FlatScene& fs, const double apex[3], const double axis[3], double cmin, double smax, unsigned long long cand_s,
                        unsigned long long cand_t, unsigned long long* ms, unsigned long long* mt) {
   *ms = 0;
   *mt = 0;
   for (unsigned long long b = cand_s; b; b &= b - 1) {
     const int i = __builtin_ctzll(b);
-    if (cone_meets_sphere(fs.spheres[i].c, fs.spheres[i].r, fs.cam_pos, axis, cmin, smax)) *ms |= 1ull << i;
+    if (cone_meets_sphere(fs.spheres[i].c, fs.spheres[i].r, apex, axis, cmin, smax)) *ms |= 1ull << i;
   }
   for (unsigned long long b = cand_t; b; b &= b - 1) {
     const int i = __builtin_ctzll(b);
-    if (cone_meets_sphere(fs.tris[i].bc, fs.tris[i].br, fs.cam_pos, axis, cmin, smax)) *mt |= 1ull << i;
+    if (cone_meets_sphere(fs.tris[i].bc, fs.tris[i].br, apex, axis, cmin, smax)) *mt |= 1ull << i;
   }
 }
 
 static unsigned long long low_bits(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
 
-void tile_primary_masks(const FlatScene& fs, int32_t W, int32_t H, const std::vector<int32_t>& tiles,
-                        std::vector<unsigned long long>* masks) {
+void tile_primary_masks(const FlatScene& fs, const CamFrame& cf, int32_t W, int32_t H,
+                        const std::vector<int32_t>& tiles, std::vector<unsigned long long>* masks) {
   masks->clear();
   const int tiles_x = (W + 31) / 32;
   const int ns = (int)fs.spheres.size(), nt = (int)fs.tris.size();
-  const double vw = 2.0 * fs.aspect;
   for (int32_t t : tiles) {
     const int tx = t % tiles_x, ty = t / tiles_x;
     double axis[3], cmin, smax;
-    rect_cone(vw, W, H, tx * 32, std::min(tx * 32 + 32, (int)W), ty * 32, std::min(ty * 32 + 32, (int)H), axis, &cmin,
+    rect_cone(cf, W, H, tx * 32, std::min(tx * 32 + 32, (int)W), ty * 32, std::min(ty * 32 + 32, (int)H), axis, &cmin,
               &smax);
     unsigned long long ms, mt;
-    cone_masks(fs, axis, cmin, smax, low_bits(std::min(ns, 64)), low_bits(std::min(nt, 64)), &ms, &mt);
+    cone_masks(fs, cf.o, axis, cmin, smax, low_bits(std::min(ns, 64)), low_bits(std::min(nt, 64)), &ms, &mt);
     masks->push_back(ms);
     masks->push_back(mt);
   }
+}
+
+// The same under the reference camera (RT_CAMERA_REFERENCE never fails)
+static CamFrame reference_frame(const FlatScene& fs, int32_t W, int32_t H) {
+  CamFrame cf;
+  (void)camera_frame(fs.camera, RT_CAMERA_REFERENCE, W, H, &cf);
+  return cf;
+}
+void tile_cost(const FlatScene& fs, int32_t W, int32_t H, const std::vector<int32_t>& tiles,
+               std::vector<float>* local_cost) {
+  tile_cost(fs, reference_frame(fs, W, H), W, H, tiles, local_cost);
+}
+void tile_primary_masks(const FlatScene& fs, int32_t W, int32_t H, const std::vector<int32_t>& tiles,
+                        std::vector<unsigned long long>* masks) {
+  tile_primary_masks(fs, reference_frame(fs, W, H), W, H, tiles, masks);
 }
 
 // ------------------------------------------------------------ partitions

@@ -43,6 +43,8 @@ RT_LAYOUT_IMAGE, RT_LAYOUT_PACKED_TILES = 0, 1
 RT_PATH_AUTO, RT_PATH_MEGAKERNEL = 0, 1
 RT_PARTITION_AUTO, RT_PARTITION_STRIDED, RT_PARTITION_BALANCED = 0, 1, 2
 SKIES = {"none": 0, "default": 1, "white": 2, "sunset": 3, "night": 4}  # RT_SKY_*
+RT_CAMERA_REFERENCE, RT_CAMERA_LOOKAT = 0, 1  # rt_settings.camera
+CAMERAS = {"reference": RT_CAMERA_REFERENCE, "lookat": RT_CAMERA_LOOKAT}
 RT_COMM_ID_BYTES = 128
 RT_MAX_FRAMES = 32  # frames per launch (rt_context_render_frames_async)
 # wavefront kernel classes (RT_WF_*, rt_context_kernel_seconds)
@@ -119,7 +121,7 @@ class Settings(ctypes.Structure):
         ("num_devices", ctypes.c_int32),
         ("seed", ctypes.c_uint64),
         ("sky", ctypes.c_int32),
-        ("_pad2", ctypes.c_int32),
+        ("camera", ctypes.c_int32),
     ]
 
 
@@ -241,6 +243,7 @@ EXPORTED_SYMBOLS = [
     "rt_scene_print_hittables",
     "rt_render",
     "rt_validate",
+    "rt_camera_frame",
     "rt_renderer_create",
     "rt_renderer_render",
     "rt_renderer_destroy",
@@ -405,6 +408,7 @@ def lib():
         "rt_context_progressive_samples": (ctypes.c_int64, [vp]),
         "rt_context_progressive_end": (ctypes.c_int, [vp]),
         "rt_rgba_delta_async": (ctypes.c_int, [vp, vp, sz, vp, vp]),
+        "rt_camera_frame": (ctypes.c_int, [ctypes.POINTER(Camera), i32, i32, i32, ctypes.POINTER(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -620,6 +624,11 @@ class ParallelRenderer:
     def set_sky(self, sky: str):
         """Opt-in sky on miss (atmosphere.go presets); "none" = black, the reference."""
         self.settings.sky = SKIES[sky]
+
+    def set_camera(self, model: str):
+        """Camera model: "reference" (getRay's fixed -Z, 90-degree view, the default) or
+        "lookat" (opt-in: the scene's own position, lookAt, up and fov; rt_camera_frame)."""
+        self.settings.camera = CAMERAS[model]
 
     def get_stats(self) -> dict:  # settings.go:27-36
         s = self.settings
@@ -901,6 +910,26 @@ def num_tiles(width: int, height: int) -> int:
 
 def tiles_for_rank(width: int, height: int, rank: int, world: int) -> int:
     return lib().rt_tiles_for_rank(width, height, rank, world)
+
+
+def camera_frame(camera, model, width: int, height: int) -> np.ndarray:
+    """rt_camera_frame: the viewport frame of `camera` (a Camera, a Scene, or a scene file's
+    camera dict) under `model` (RT_CAMERA_* or its name) for a width x height image, as 12
+    float64: origin, lower_left, horizontal, vertical."""
+    if isinstance(camera, Scene):
+        camera = camera.view.camera
+    elif isinstance(camera, dict):
+        cam = Camera()
+        cam.position[:] = camera.get("position", (0, 0, 0))
+        cam.look_at[:] = camera.get("lookAt", (0, 0, 0))
+        cam.up[:] = camera.get("up", (0, 0, 0))
+        cam.fov = camera.get("fov", 0.0)
+        cam.aspect_ratio = camera.get("aspectRatio", 0.0)
+        camera = cam
+    out = np.zeros(12, np.float64)
+    _check(lib().rt_camera_frame(ctypes.byref(camera), CAMERAS.get(model, model), width, height,
+                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return out
 
 
 def render(scene: Scene, width: int, height: int, settings: Settings):

@@ -20,7 +20,8 @@
 // exactly as the C++ loader does for a file.  One rt_renderer per
 // ParallelRenderer holds the devices' scenes, schedules and buffers between
 // calls (NewParallelRenderer once, Render per frame); RT_DEVICES sets how many
-// GPUs it shards the tiles over (default 1).
+// GPUs it shards the tiles over (default 1), RT_CAMERA=lookat opts in to the
+// scene's own camera orientation and field of view (rt_settings.camera).
 //
 // Go cannot run in the image this was written in (no toolchain, SURVEY.md
 // §8c): tests/c/shim_sequence.c makes exactly this file's C call sequence
@@ -129,6 +130,12 @@ func (r *ParallelRenderer) RenderGPU(s *scene.Scene, width, height int) *image.R
 	st.soft_shadows = cbool(r.softShadows)
 	st.depth_of_field = cbool(r.depthOfField)
 	st.num_workers = C.int32_t(r.numWorkers)
+	// getRay's fixed -Z view (renderer.go:377-390) unless RT_CAMERA=lookat opts
+	// in to the scene's own lookAt / up / fov (rt_api.h RT_CAMERA_*)
+	st.camera = C.RT_CAMERA_REFERENCE
+	if os.Getenv("RT_CAMERA") == "lookat" {
+		st.camera = C.RT_CAMERA_LOOKAT
+	}
 
 	img := image.NewRGBA(image.Rect(0, 0, width, height))
 	var stats C.rt_stats

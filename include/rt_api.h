@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 7  /* 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame; 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -90,8 +90,9 @@ typedef struct {
 } rt_light;
 
 /* Camera — scene.go:18-24.  Only position and aspect_ratio are used by the
- * reference's getRay (renderer.go:377-390); the others are carried for
- * fidelity. */
+ * reference's getRay (renderer.go:377-390), which is RT_CAMERA_REFERENCE, the
+ * default; look_at, up and fov (the vertical field of view in degrees) are
+ * read by the opt-in RT_CAMERA_LOOKAT model (rt_settings.camera). */
 typedef struct {
   double position[3];
   double look_at[3];
@@ -126,8 +127,18 @@ typedef struct {
   int32_t num_devices;           /* rt_render: GPUs 0..n-1 render tiles t % n (0 or 1: device 0 only) */
   uint64_t seed;                 /* counter-based RNG seed (include/rt_rng.h); default 1 */
   int32_t sky;                   /* RT_SKY_*: radiance of a ray that hits nothing; default RT_SKY_NONE */
-  int32_t _pad2;
+  int32_t camera;                /* RT_CAMERA_*: which camera model shoots the primary rays; default RT_CAMERA_REFERENCE */
 } rt_settings;
+
+/* The camera model.  RT_CAMERA_REFERENCE is the reference's getRay
+ * (renderer.go:377-390): rays from camera.position down -Z through a fixed
+ * 90-degree viewport of width 2 * aspect_ratio, whatever look_at, up and fov
+ * say -- the default and the parity setting.  RT_CAMERA_LOOKAT is OPT-IN and
+ * honours the scene's own camera: see rt_camera_frame for its definition.
+ * Image row 0 is the BOTTOM of the viewport in both models (the image is
+ * vertically flipped vs the camera's up, exactly like the reference). */
+#define RT_CAMERA_REFERENCE 0
+#define RT_CAMERA_LOOKAT 1
 
 /* What a ray that hits nothing returns.  The reference's live path returns
  * black (traceRay, renderer.go:170-173): RT_SKY_NONE, the default and the
@@ -249,6 +260,30 @@ int rt_render(const rt_scene* scene, int32_t width, int32_t height, const rt_set
 /* The argument checks rt_render makes before it touches a device (scene
  * arrays and kinds; 1 <= W, H <= 65536; samples range): RT_OK or RT_E_INVALID. */
 int rt_validate(const rt_scene* scene, int32_t width, int32_t height, const rt_settings* settings);
+
+/* The viewport frame of `cam` under camera model `model` (RT_CAMERA_*) for a
+ * width x height image: out = origin, lower_left, horizontal, vertical, three
+ * doubles each, in plain binary64 with Go Vec3 semantics and this order:
+ *   reference: horizontal = (2 * aspect_ratio, 0, 0), vertical = (0, 2, 0),
+ *     lower_left = origin - horizontal/2 - vertical/2 - (0, 0, 1)
+ *     (getRay, renderer.go:377-390);
+ *   look-at:   w = normalize(position - look_at), U = normalize(cross(up, w)),
+ *     V = cross(w, U); h = 1.0 when fov == 90, else tan(fov * (pi / 360));
+ *     a = aspect_ratio, or (double)width / height when aspect_ratio is 0;
+ *     horizontal = U * (2 h a), vertical = V * (2 h),
+ *     lower_left = origin - horizontal/2 - vertical/2 - w.
+ * The exact 1.0 at 90 degrees (tan(pi/4) rounds to 0.9999999999999999) makes
+ * a look-at camera that looks down -Z with up +Y shoot the reference's rays
+ * bit for bit.  The ray of image coordinates (u, v) is, per component,
+ * ((lower_left + horizontal * u) + vertical * v) - origin, not normalised;
+ * row 0 of the image is v in [0, 1/height): the BOTTOM of the viewport.
+ * RT_E_INVALID (with a message) for an unknown model and, in look-at mode,
+ * for a camera whose fields are not finite, position == look_at, cross(up, w)
+ * of zero length (a zero up included), fov outside (0, 180) or
+ * aspect_ratio < 0 -- the checks rt_validate and every render entry point
+ * make in look-at mode.  The reference model reads position and aspect_ratio
+ * only and checks nothing. */
+int rt_camera_frame(const rt_camera* cam, int32_t model, int32_t width, int32_t height, double out[12]);
 
 /* ------------------------------------------ persistent multi-GPU renderer */
 
