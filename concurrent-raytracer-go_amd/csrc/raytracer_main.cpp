@@ -4,7 +4,8 @@
 //             [--samples N] [--max-depth N] [--seed N] [--no-soft-shadows]
 //             [--no-recursive] [--devices N] [--watchdog SECONDS]
 //             [--sky default|white|sunset|night] [--camera reference|lookat]
-//             [--pass-samples N [--time-budget SECONDS] [--converge PIXELS]]
+//             [--pass-samples N [--time-budget SECONDS] [--converge PIXELS]
+//              [--adaptive TOL[,PATIENCE[,MIN]]] [--count-map FILE]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -20,7 +21,10 @@
 // "Pass k: n samples[, c pixels changed]" line per pass, stopping early once
 // --time-budget SECONDS have passed or at most --converge PIXELS pixels of the
 // preview changed in a pass; the output is written once, at the end, and
-// benchmark_data.json records the samples actually rendered.
+// benchmark_data.json records the samples actually rendered.  --adaptive
+//  stops every pixel on its own and the run once none is
+// active ("Pass k: n samples, a pixels active"); --count-map FILE writes the
+// per-pixel sample counts as a grey PNG, count * 255 / cap.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -111,7 +115,7 @@ static void print_complete() {
 // SaveBenchmarkData (renderer.go:473-485): BenchmarkData JSON, 2-space indent,
 // next to the output (main.go:64-69)
 static void save_benchmark(const std::string& out_path, long long w, long long h, const rt_settings& st,
-                           const rt_stats& stats) {
+                           const rt_stats& stats, double mean_samples = -1) {
   std::string bench_path = dir_of(out_path) + "/benchmark_data.json";
   FILE* f = fopen(bench_path.c_str(), "wb");
   if (!f) {
@@ -122,6 +126,8 @@ static void save_benchmark(const std::string& out_path, long long w, long long h
     fprintf(f, "  \"resolution\": \"%lldx%lld\",\n", w, h);
     fprintf(f, "  \"render_time_seconds\": %.17g,\n", stats.render_seconds);
     fprintf(f, "  \"samples\": %d,\n", st.samples);
+    // (--adaptive: the mean samples per pixel actually rendered)
+    if (mean_samples >= 0) fprintf(f, "  \"mean_samples_per_pixel\": %.17g,\n", mean_samples);
     fprintf(f, "  \"max_depth\": %d,\n", st.max_depth);
     fprintf(f, "  \"num_workers\": %d,\n", st.num_workers);
     fprintf(f, "  \"objects\": %d,\n", stats.objects);
@@ -150,9 +156,14 @@ static void save_benchmark(const std::string& out_path, long long w, long long h
 // --pass-samples: the frame through rt_context_progressive_* on device 0,
 // pass_samples at a time up to the cap st.samples; fills rgba (host, w*h*4),
 // stats and *rendered (samples per pixel actually rendered).  budget_s < 0 /
-// converge < 0: that rule is off.
+// converge < 0: that rule is off.  adapt (--adaptive; null:
+// off): every pixel stops on its own, the progression also ends when none is
+// active; *mean_samples is the mean samples per pixel, and count_map (when
+// not empty) receives the counts as a grey PNG, count * 255 / cap.
 static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int pass_samples,
-                              double budget_s, long long converge, uint8_t* rgba, rt_stats* stats, int* rendered) {
+                              double budget_s, long long converge, const rt_adaptive* adapt,
+                              const std::string& count_map, uint8_t* rgba, rt_stats* stats, int* rendered,
+                              double* mean_samples) {
   const auto t_new = std::chrono::steady_clock::now();
   rt_context* ctx = nullptr;
   if (rt_context_create(0, &ctx) != RT_OK) return RT_E_DEVICE;
@@ -170,6 +181,8 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
     return false;
   };
   if (rc == RT_OK) rc = rt_context_progressive_begin(ctx, w, h, &st, 0, 1, RT_LAYOUT_IMAGE);
+  if (rc == RT_OK && adapt) rc = rt_context_progressive_set_adaptive(ctx, adapt);
+  int64_t state[4] = {0, 0, 0, 0};
   if (rc == RT_OK && hip_ok(hipMalloc((void**)&d_img[0], npix * 4), "hipMalloc") &&
       hip_ok(hipMalloc((void**)&d_img[1], npix * 4), "hipMalloc"))
     hip_ok(hipMalloc((void**)&d_delta, 2 * sizeof(uint32_t)), "hipMalloc");
@@ -192,17 +205,42 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
     if (rt_context_last_kernel_seconds(ctx, &ks) == RT_OK) kernel_s += ks;
     done += n;
     k += 1;
-    if (k > 1)
+    if (adapt) {
+      rc = rt_context_progressive_state(ctx, state);
+      if (rc != RT_OK) break;
+      printf("Pass %d: %d samples, %lld pixels active\n", k, done, (long long)state[1]);
+    } else if (k > 1)
       printf("Pass %d: %d samples, %u pixels changed\n", k, done, delta[0]);
     else
       printf("Pass %d: %d samples\n", k, done);
     fflush(stdout);
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (adapt && state[1] == 0) break;
     if (done >= st.samples || (budget_s >= 0 && el >= budget_s) || (converge >= 0 && k > 1 && (long long)delta[0] <= converge))
       break;
   }
   if (rc == RT_OK && k > 0)
     hip_ok(hipMemcpy(rgba, d_img[(k - 1) & 1], npix * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+  if (rc == RT_OK) rc = rt_context_progressive_state(ctx, state);
+  if (rc == RT_OK) *mean_samples = state[0] > 0 ? (double)state[2] / (double)state[0] : 0.0;
+  if (rc == RT_OK && !count_map.empty()) {
+    uint32_t* d_counts = nullptr;
+    std::vector<uint32_t> counts(npix);
+    std::vector<uint8_t> grey(npix * 4);
+    if (hip_ok(hipMalloc((void**)&d_counts, npix * sizeof(uint32_t)), "hipMalloc")) {
+      rc = rt_context_progressive_counts_async(ctx, d_counts, nullptr);
+      if (rc == RT_OK) hip_ok(hipMemcpy(counts.data(), d_counts, npix * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy");
+      (void)hipFree(d_counts);
+    }
+    if (rc == RT_OK) {
+      for (size_t i = 0; i < npix; ++i) {
+        const uint8_t g = (uint8_t)std::min<uint64_t>(255, (uint64_t)counts[i] * 255 / (uint64_t)std::max(st.samples, 1));
+        grey[4 * i + 0] = grey[4 * i + 1] = grey[4 * i + 2] = g;
+        grey[4 * i + 3] = 255;
+      }
+      rc = rt_write_png(count_map.c_str(), grey.data(), w, h);
+    }
+  }
   const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   (void)rt_context_progressive_end(ctx);
@@ -228,6 +266,9 @@ int main(int argc, char** argv) {
   double watchdog_s = 0;  // --watchdog (0: no bound, as Go's Render)
   long long pass_samples = 0, converge = -1;  // --pass-samples (0: one render), --converge (-1: off)
   double budget_s = -1;                       // --time-budget (-1: off)
+  bool adaptive_on = false;                   // --adaptive TOL[,PATIENCE[,MIN]]
+  rt_adaptive adapt = {0, 1, 0, 0};
+  std::string count_map;                      // --count-map FILE
   rt_settings st;
   rt_settings_default(&st);
   st.num_workers = (int32_t)sysconf(_SC_NPROCESSORS_ONLN);  // runtime.NumCPU(), main.go:46
@@ -287,6 +328,31 @@ int main(int argc, char** argv) {
         return 2;
       }
       converge = v;
+    } else if (a == "--adaptive") {  // progressive: every pixel stops on its own
+      const std::string x = need("--adaptive");
+      long long f[3] = {0, 1, 0};
+      size_t pos = 0;
+      int nf = 0;
+      bool ok = !x.empty();
+      while (ok && nf < 3) {
+        const size_t c = x.find(',', pos);
+        const std::string part = x.substr(pos, c == std::string::npos ? std::string::npos : c - pos);
+        ok = parse_int(part.c_str(), &f[nf]);
+        nf += 1;
+        if (c == std::string::npos) break;
+        pos = c + 1;
+        if (nf == 3) ok = false;  // a fourth field
+      }
+      if (!ok || f[0] < 0 || f[0] > 255 || f[1] < 1 || f[1] > (1 << 24) || f[2] < 0 || f[2] > (1 << 24)) {
+        fprintf(stderr, "invalid --adaptive %s (TOL[,PATIENCE[,MIN]]: 0..255, >= 1, >= 0)\n", x.c_str());
+        return 2;
+      }
+      adapt.tolerance = (int32_t)f[0];
+      adapt.patience = (int32_t)f[1];
+      adapt.min_samples = (int32_t)f[2];
+      adaptive_on = true;
+    } else if (a == "--count-map") {  // --adaptive: the per-pixel sample counts as a grey PNG
+      count_map = need("--count-map");
     } else if (a == "--sky") {  // opt-in sky on miss (atmosphere.go presets); default: black
       const std::string k = need("--sky");
       if (k == "none") st.sky = RT_SKY_NONE;
@@ -320,6 +386,14 @@ int main(int argc, char** argv) {
   }
   if (pass_samples == 0 && (budget_s >= 0 || converge >= 0)) {
     fprintf(stderr, "--time-budget and --converge need --pass-samples\n");
+    return 2;
+  }
+  if (pass_samples == 0 && (adaptive_on || !count_map.empty())) {
+    fprintf(stderr, "--adaptive and --count-map need --pass-samples\n");
+    return 2;
+  }
+  if (adaptive_on && st.sky != RT_SKY_NONE) {
+    fprintf(stderr, "--adaptive does not support --sky\n");
     return 2;
   }
   if (args.size() < 4) {
@@ -399,9 +473,11 @@ int main(int argc, char** argv) {
     rt_stats stats;
     memset(&stats, 0, sizeof stats);
     int rendered = 0;
+    double mean_samples = -1;
     if (rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK ||
         render_progressive(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)pass_samples, budget_s, converge,
-                           rgba.data(), &stats, &rendered) != RT_OK) {
+                           adaptive_on ? &adapt : nullptr, count_map, rgba.data(), &stats, &rendered,
+                           &mean_samples) != RT_OK) {
       fprintf(stderr, "render failed: %s\n", rt_last_error());
       rt_scene_free(sb);
       return 2;
@@ -420,7 +496,7 @@ int main(int argc, char** argv) {
     }
     rt_settings done_st = st;
     done_st.samples = rendered;  // (the samples actually rendered)
-    save_benchmark(out_path, w, h, done_st, stats);
+    save_benchmark(out_path, w, h, done_st, stats, adaptive_on ? mean_samples : -1);
     rt_scene_free(sb);
     return 0;
   }

@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/rt_adaptive.h"
 #include "../../include/rt_rng.h"
 #include "rt_internal.h"
 
@@ -135,7 +136,7 @@ struct rt_context {
   unsigned long long* dbg = nullptr;
   // the work schedule (rt_schedule.hip), cached per (scene, W, H, rank, world, settings)
   uint64_t scene_gen = 0;
-  int64_t order_key[14] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int64_t order_key[15] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   int32_t* d_blocks = nullptr;  // work blocks, kBlockInts ints each, heaviest first
   size_t d_blocks_cap = 0;  // bytes
   int32_t num_blocks = 0;
@@ -219,6 +220,20 @@ struct rt_context {
   int64_t prog_done = 0;
   void* d_prog = nullptr;
   size_t prog_cap = 0;
+  // adaptive sampling of the progression: the rule, the
+  // per-pixel state ([totals, 256 B][count][streak][active][rgba], one word
+  // per local pixel each), the totals of the last add read back into pinned
+  // memory (active pixels, sum of counts), the in-image pixels of the rank's
+  // tiles, the adds so far, and the generation of the active set: it grows
+  // when an add stopped pixels, and keys the adaptive adds' schedules
+  bool adapt_on = false;
+  rt_adaptive adapt{};
+  char* d_adapt = nullptr;
+  size_t adapt_cap = 0;
+  unsigned long long* h_adapt = nullptr;
+  int64_t adapt_inimg = 0, adapt_active = 0, adapt_sum = 0, adapt_gen = 0;
+  int64_t prog_adds = 0;
+  bool adapt_pending = false;  // an add's totals are on their way to h_adapt
 };
 
 // Events for kernel classes [first, last] of one launch sequence: ev[k] opens
@@ -498,10 +513,11 @@ void rt_context_destroy(rt_context* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_scene, (void*)c->d_counts, (void*)c->d_blocks, (void*)c->d_pilot, c->d_acc,
                   (void*)c->d_meas, (void*)c->d_split, (void*)c->d_sched, (void*)c->d_part, c->wf_mem, c->wf_rad,
-                  (void*)c->wf_ctl, (void*)c->d_tail, (void*)c->d_live, (void*)c->d_rows, c->d_prog})
+                  (void*)c->wf_ctl, (void*)c->d_tail, (void*)c->d_live, (void*)c->d_rows, c->d_prog, (void*)c->d_adapt})
     dev_free(p);
   host_free(c->h_stage);
   host_free(c->h_small);
+  host_free(c->h_adapt);
   if (c->wf_host) (void)hipHostFree(c->wf_host);
   for (hipEvent_t& e : c->wf_ev)
     if (e) (void)hipEventDestroy(e);
@@ -877,7 +893,11 @@ static bool stream_wanted(const rt_context* c, const KParams& p, const rt_settin
          tn.tail_helpers < 0 && !tn.measure;
 }
 
-static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream_t s, int frames = 1) {
+// active (an adaptive progression's add): the per-pixel active
+// flags folded into the pixels' primary masks, the schedule keyed by the
+// active set's generation `active_gen`; null: an ordinary schedule.
+static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream_t s, int frames = 1,
+                            const uint32_t* active = nullptr, int64_t active_gen = 0) {
   const FlatScene& f = c->flat;
   const int w = p->W, h = p->H, rank = p->rank, world = p->world;
   const rt_tuning& tn = c->tun;
@@ -891,13 +911,19 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
   const bool sky = st->sky != RT_SKY_NONE;
   const bool frustum = tn.frustum != 0 && !sky;
   const bool part = use_partition(c, w, h, world);
-  const int64_t key[14] = {(int64_t)c->scene_gen, w, h, rank, world, st->samples, st->max_depth,
+  const int64_t key[15] = {(int64_t)c->scene_gen, w, h, rank, world, st->samples, st->max_depth,
                            st->recursive_reflections, st->soft_shadows, bigP, (int64_t)(block_work * 16),
                            (pilot ? 1 + tn.pilot_depth : 0) | (int64_t)tn.split_samples << 16,
                            (frustum ? 1 : 0) | (sky ? 2 : 0) | (tn.measure ? 4 : 0) | (want_live ? 8 : 0) | (st->camera ? 16 : 0) |
                                (int64_t)tn.split_depth << 8,
-                           part ? (int64_t)c->part->id : 0};
-  const bool masks = masks_apply(f);
+                           part ? (int64_t)c->part->id : 0,
+                           active ? active_gen + 1 : 0};
+  // the pixels' primary masks: the scene's candidate masks where they apply; an
+  // adaptive add without them (or without primary culling) gets masks of its
+  // own that hold every primitive and only carry the active flags
+  const bool prim_masks = masks_apply(f);
+  const bool own_masks = active && !(prim_masks && frustum);
+  const bool masks = prim_masks || own_masks;
   const bool new_key = memcmp(key, c->order_key, sizeof key) != 0;
   // a measured re-cut: the previous frame of this key measured every pixel
   const bool remeasured = !new_key && c->meas_state == 2;
@@ -916,7 +942,18 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
     c->d_masks = nullptr;
     if (local > 0) {
       // per-tile inputs (host): primary-ray candidate masks, projected-primitive counts
-      if (masks) tile_primary_masks(f, p->cf, w, h, tiles, &c->masks_host);
+      if (own_masks) {
+        auto bits = [](size_t n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; };
+        const unsigned long long ms = prim_masks ? bits(f.spheres.size()) : ~0ull;
+        const unsigned long long mt = prim_masks ? bits(f.tris.size()) : ~0ull;
+        c->masks_host.resize((size_t)local * 2);
+        for (int lt = 0; lt < local; ++lt) {
+          c->masks_host[2 * lt] = ms;
+          c->masks_host[2 * lt + 1] = mt;
+        }
+      } else if (masks) {
+        tile_primary_masks(f, p->cf, w, h, tiles, &c->masks_host);
+      }
       std::vector<float> cost;
       tile_cost(f, p->cf, w, h, tiles, &cost);
       const size_t scratch = sched_scratch_bytes(local);
@@ -959,6 +996,8 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
         return fail_synced(RT_E_DEVICE);
       SchedParams sp = sched_params(c, *p, st, tiles, dev_tiles(c, w, h, rank, world), masks, frustum, block_work,
                                     bigP, c->d_sched, c->d_masks, d_cost);
+      sp.active = active;
+      sp.own_masks = own_masks ? 1 : 0;
       int e = sched_launch_pixels(sp, s);
       if (e != hipSuccess) {
         set_error(std::string("schedule launch failed: ") + hipGetErrorString((hipError_t)e));
@@ -1047,7 +1086,7 @@ static int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hi
   p->split_rad = c->nsplit ? (double*)c->d_split : nullptr;
   p->split_hits = c->nsplit ? (uint32_t*)((char*)c->d_split + rows * nf) : nullptr;
   p->split_cnt = c->nsplit ? (int32_t*)(p->split_hits + (size_t)c->nsplit * ((st->samples + 31) / 32) * nf) : nullptr;
-  p->tile_masks = (masks && frustum) ? c->d_masks : nullptr;
+  p->tile_masks = ((masks && frustum) || active) ? c->d_masks : nullptr;
   return RT_OK;
 }
 
@@ -1079,7 +1118,8 @@ static int wf_shard_cap(int nl, const rt_tuning& tn, uint64_t samples) {
   return (int)(std::max(1ll, cap / per) * kWfBlockSlots);
 }
 
-static int render_wavefront(rt_context* c, const KParams& kp, const rt_settings* st, hipStream_t s, bool count) {
+static int render_wavefront(rt_context* c, const KParams& kp, const rt_settings* st, hipStream_t s, bool count,
+                            const uint32_t* active = nullptr) {
   const FlatScene& f = c->flat;
   if (c->prof_on) {  // the last frame's kernel times (its events are reused)
     int rc = prof_collect(c);
@@ -1246,7 +1286,8 @@ static int render_wavefront(rt_context* c, const KParams& kp, const rt_settings*
       // host reads the loop state one bounce behind the GPU
       p.live_bound = (int32_t)cap;
       p.dry = 0;
-      int e = wf_launch_bounce(p, true, count, s, prof_block(c, kWfRegen, kWfRegen));
+      // (active: an adaptive add -- stopped pixels' samples become dead slots)
+      int e = wf_launch_bounce(p, true, count, s, prof_block(c, kWfRegen, kWfRegen), active);
       if (e) return fail(e, "launch");
       std::swap(p.cur, p.next);
       const long long max_iter = (long long)total + std::max(kp.max_depth, 0) + 8;
@@ -1255,7 +1296,7 @@ static int render_wavefront(rt_context* c, const KParams& kp, const rt_settings*
           set_error("wavefront loop did not terminate");
           return RT_E_DEVICE;
         }
-        e = wf_launch_bounce(p, false, count, s, prof_block(c, kWfExtend, kWfRegen));
+        e = wf_launch_bounce(p, false, count, s, prof_block(c, kWfExtend, kWfRegen), active);
         if (e) return fail(e, "launch");
         std::swap(p.cur, p.next);
         const int r = (int)(it % kWfRing);
@@ -1853,8 +1894,179 @@ int rt_context_progressive_begin(rt_context* c, int32_t w, int32_t h, const rt_s
   c->prog_layout = layout;
   c->prog_st = *st;
   c->prog_done = 0;
+  c->prog_adds = 0;
+  c->adapt_on = false;  // (adaptive sampling is off after every begin)
+  c->adapt_pending = false;
   c->prog_on = true;
   return RT_OK;
+}
+
+// ---- adaptive sampling
+// The in-image pixels of the progression's tiles.
+static int64_t prog_image_pixels(const rt_context* c) {
+  std::vector<int32_t> tiles;
+  host_tiles(c, c->prog_w, c->prog_h, c->prog_rank, c->prog_world, &tiles);
+  const int tiles_x = (c->prog_w + 31) / 32, ntiles = rt_num_tiles(c->prog_w, c->prog_h);
+  int64_t n = 0;
+  for (int32_t t : tiles) {
+    if (t < 0 || t >= ntiles) continue;
+    const int x0 = (t % tiles_x) * 32, y0 = (t / tiles_x) * 32;
+    n += (int64_t)std::max(0, std::min(32, c->prog_w - x0)) * std::max(0, std::min(32, c->prog_h - y0));
+  }
+  return n;
+}
+
+// The state arrays and frame of the progression, as the adaptive kernels take them.
+static void adapt_params(const rt_context* c, AdaptParams* a) {
+  memset(a, 0, sizeof *a);
+  const int w = c->prog_w, h = c->prog_h, rank = c->prog_rank, world = c->prog_world;
+  const size_t npx = (size_t)local_tiles(c, w, h, rank, world) * 1024;
+  a->acc = (const double*)c->d_prog;
+  if (c->adapt_on) {
+    a->totals = (unsigned long long*)c->d_adapt;
+    a->count = (uint32_t*)(c->d_adapt + 256);
+    a->streak = a->count + npx;
+    a->active = a->streak + npx;
+    a->rgba = a->active + npx;
+  }
+  a->tile_list = dev_tiles(c, w, h, rank, world);
+  a->npix = (int32_t)npx;
+  a->W = w;
+  a->H = h;
+  a->rank = rank;
+  a->world = world;
+  a->tiles_x = (w + 31) / 32;
+  a->ntiles = rt_num_tiles(w, h);
+  a->layout = c->prog_layout;
+  a->tolerance = c->adapt.tolerance;
+  a->patience = c->adapt.patience;
+  a->min_samples = c->adapt.min_samples;
+}
+
+static bool adaptive_ok(const rt_adaptive* a) {
+  return a->tolerance >= 0 && a->tolerance <= 255 && a->patience >= 1 && a->min_samples >= 0;
+}
+
+// The totals of the last adaptive add (its update kernel's counts), once it has finished.
+static int adapt_collect(rt_context* c) {
+  if (!c->adapt_pending) return RT_OK;
+  const int rc = quiesce(c);
+  if (rc) return rc;
+  const int64_t active = (int64_t)c->h_adapt[0];
+  if (active != c->adapt_active) c->adapt_gen += 1;  // pixels stopped: the next add's schedule leaves them out
+  c->adapt_active = active;
+  c->adapt_sum = (int64_t)c->h_adapt[1];
+  c->adapt_pending = false;
+  return RT_OK;
+}
+
+int rt_context_progressive_set_adaptive(rt_context* c, const rt_adaptive* a) {
+  if (!c || !c->prog_on || !c->have_scene) {
+    set_error("rt_context_progressive_set_adaptive: the context has no progression (none begun, or it was ended)");
+    return RT_E_INVALID;
+  }
+  if (c->prog_adds > 0) {
+    set_error("rt_context_progressive_set_adaptive: the progression already has samples (call it before the first add)");
+    return RT_E_INVALID;
+  }
+  if (!a) {
+    c->adapt_on = false;
+    return RT_OK;
+  }
+  if (!adaptive_ok(a)) {
+    set_error("rt_context_progressive_set_adaptive: tolerance must be in 0..255, patience >= 1, min_samples >= 0");
+    return RT_E_INVALID;
+  }
+  if (c->prog_st.sky != RT_SKY_NONE) {
+    set_error("rt_context_progressive_set_adaptive: adaptive sampling does not support a sky (sky must be RT_SKY_NONE)");
+    return RT_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t npx = (size_t)local_tiles(c, c->prog_w, c->prog_h, c->prog_rank, c->prog_world) * 1024;
+  int rc = grow(c, &c->d_adapt, &c->adapt_cap, 256 + std::max<size_t>(npx, 1) * 4 * sizeof(uint32_t));
+  if (rc) return rc;
+  if (!c->h_adapt) HIP_TRY((hipError_t)host_alloc((void**)&c->h_adapt, 256));
+  rc = quiesce(c);  // (an earlier adaptive progression's last add may still use the state)
+  if (rc) return rc;
+  // totals, counts and streaks 0; every pixel active; no kept image yet
+  HIP_TRY(hipMemsetAsync(c->d_adapt, 0, 256 + npx * 2 * sizeof(uint32_t), c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_adapt + 256 + npx * 2 * sizeof(uint32_t), 1, npx * sizeof(uint32_t), c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_adapt + 256 + npx * 3 * sizeof(uint32_t), 0, npx * sizeof(uint32_t), c->stream));
+  rc = wait_stream(c, c->stream);
+  if (rc) return rc;
+  c->adapt = *a;
+  c->adapt._pad = 0;
+  c->adapt_inimg = prog_image_pixels(c);
+  c->adapt_active = c->adapt_inimg;
+  c->adapt_sum = 0;
+  c->adapt_gen += 1;  // (a new active set: no schedule of an earlier progression fits it)
+  c->adapt_pending = false;
+  c->adapt_on = true;
+  return RT_OK;
+}
+
+int rt_context_progressive_counts_async(rt_context* c, uint32_t* d_counts, void* stream) {
+  if (!c || !c->prog_on || !c->have_scene) {
+    set_error("rt_context_progressive_counts_async: the context has no progression (none begun, or it was ended)");
+    return RT_E_INVALID;
+  }
+  if (!d_counts) {
+    set_error("rt_context_progressive_counts_async: d_counts is NULL");
+    return RT_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (c->have_timing && s != c->last_stream) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
+  AdaptParams a;
+  adapt_params(c, &a);
+  const int e = launch_progressive_counts(a, (uint32_t)c->prog_done, d_counts, s);
+  if (e != hipSuccess) {
+    set_error(std::string("progressive counts launch failed: ") + hipGetErrorString((hipError_t)e));
+    return RT_E_DEVICE;
+  }
+  return RT_OK;
+}
+
+int rt_context_progressive_state(rt_context* c, int64_t out[4]) {
+  if (!c || !c->prog_on || !c->have_scene) {
+    set_error("rt_context_progressive_state: the context has no progression (none begun, or it was ended)");
+    return RT_E_INVALID;
+  }
+  if (!out) {
+    set_error("rt_context_progressive_state: out is NULL");
+    return RT_E_INVALID;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = quiesce(c);  // waits for the last add
+  if (rc) return rc;
+  if (c->adapt_on) {
+    rc = adapt_collect(c);
+    if (rc) return rc;
+    out[0] = c->adapt_inimg;
+    out[1] = c->adapt_active;
+    out[2] = c->adapt_sum;
+  } else {
+    out[0] = out[1] = prog_image_pixels(c);
+    out[2] = out[0] * c->prog_done;
+  }
+  out[3] = c->prog_adds;
+  return RT_OK;
+}
+
+int rt_adaptive_step(const uint8_t old_rgba[4], const uint8_t new_rgba[4], int32_t had_image, int32_t count,
+                     int32_t streak, const rt_adaptive* a, int32_t* new_streak) {
+  if (!old_rgba || !new_rgba || !a || !new_streak) {
+    set_error("rt_adaptive_step: NULL argument");
+    return RT_E_INVALID;
+  }
+  if (!adaptive_ok(a) || count < 0 || streak < 0) {
+    set_error("rt_adaptive_step: tolerance must be in 0..255, patience >= 1, min_samples, count and streak >= 0");
+    return RT_E_INVALID;
+  }
+  uint32_t o = 0, n = 0;
+  memcpy(&o, old_rgba, 4);
+  memcpy(&n, new_rgba, 4);
+  return rt_adaptive_rule(o, n, had_image != 0, count, streak, a->tolerance, a->patience, a->min_samples, new_streak);
 }
 
 int rt_context_progressive_add_async(rt_context* c, int32_t nsamples, float* d_linear, uint8_t* d_rgba,
@@ -1871,12 +2083,51 @@ int rt_context_progressive_add_async(rt_context* c, int32_t nsamples, float* d_l
   HIP_TRY(hipSetDevice(c->device));
   const rt_settings* st = &c->prog_st;
   const int w = c->prog_w, h = c->prog_h, rank = c->prog_rank, world = c->prog_world;
+  // adaptive: the render launches below only carry the sums
+  // of the pixels still active (no image pointers, the active flags folded
+  // into the schedule / the wavefront's sample ids); adaptive_update_kernel
+  // then applies the stop rule and writes the image of every pixel.  The add
+  // first learns how many pixels the last one left active (its totals).
+  const bool adaptive = c->adapt_on;
+  AdaptParams ap;
+  if (adaptive) {
+    int rc = adapt_collect(c);
+    if (rc) return rc;
+    adapt_params(c, &ap);
+    ap.n = nsamples;
+    ap.out_linear = d_linear;
+    ap.out_rgba = d_rgba;
+  }
+  const uint32_t* active = adaptive ? ap.active : nullptr;
   KParams p;
   base_params(c, w, h, st, rank, world, c->prog_layout, &p);
-  p.out_linear = d_linear;
-  p.out_rgba = d_rgba;
+  p.out_linear = adaptive ? nullptr : d_linear;
+  p.out_rgba = adaptive ? nullptr : d_rgba;
   hipStream_t s = (hipStream_t)stream;
   if (c->have_timing && s != c->last_stream) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
+  // Enqueued after an adaptive add's render launches: the update, and its totals to the host
+  auto adaptive_finish = [&]() -> int {
+    const int e = launch_adaptive_update(ap, s);
+    if (e != hipSuccess) {
+      set_error(std::string("adaptive update launch failed: ") + hipGetErrorString((hipError_t)e));
+      return RT_E_DEVICE;
+    }
+    HIP_TRY(hipMemcpyAsync(c->h_adapt, ap.totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    c->adapt_pending = true;
+    return RT_OK;
+  };
+  if (adaptive && c->adapt_active == 0) {
+    // every pixel has stopped: nothing to render, the image is written all the same
+    HIP_TRY(hipEventRecord(c->ev0, s));
+    const int rc = adaptive_finish();
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->ev1, s));
+    c->last_stream = s;
+    c->have_timing = true;
+    c->prog_done += nsamples;
+    c->prog_adds += 1;
+    return RT_OK;
+  }
   const bool wf = use_wavefront(c);
   // more than a block holds: sub-passes, as a frame's sample passes (render_one);
   // only the last one writes the image
@@ -1894,13 +2145,13 @@ int rt_context_progressive_add_async(rt_context* c, int32_t nsamples, float* d_l
     p.acc_mode = 1 | (pass < npass - 1 ? 2 : 4);
     if (!wf) {
       // (keyed by the add's sample count, not by sample_base: equal adds share a schedule)
-      int rc = prepare_schedule(c, &p, &ps, s, 1);
+      int rc = prepare_schedule(c, &p, &ps, s, 1, active, c->adapt_gen);
       if (rc) return rc;
     }
     p.num_wgs = p.num_blocks;
     if (pass == 0) HIP_TRY(hipEventRecord(c->ev0, s));
     if (wf) {
-      int rc = render_wavefront(c, p, &ps, s, false);
+      int rc = render_wavefront(c, p, &ps, s, false, active);
       if (rc) return rc;
     } else {
       bool streamed = false;
@@ -1915,12 +2166,17 @@ int rt_context_progressive_add_async(rt_context* c, int32_t nsamples, float* d_l
       }
     }
   }
+  if (adaptive) {
+    const int rc = adaptive_finish();
+    if (rc) return rc;
+  }
   HIP_TRY(hipEventRecord(c->ev1, s));
   c->stats.frames += 1;
   c->stats.launches += npass;
   c->last_stream = s;
   c->have_timing = true;
   c->prog_done += nsamples;
+  c->prog_adds += 1;
   return RT_OK;
 }
 
@@ -1932,6 +2188,7 @@ int rt_context_progressive_end(rt_context* c) {
     return RT_E_INVALID;
   }
   c->prog_on = false;
+  c->adapt_on = false;
   if (!c->d_prog) return RT_OK;
   HIP_TRY(hipSetDevice(c->device));
   int rc = quiesce(c);  // the last add may still use the sums

@@ -125,6 +125,13 @@ struct SchedParams {
   int32_t* live_cursor;        // per weight class: next list position
   int32_t* live;               // the list, heaviest class first, 4 ints each: {x, y, y * W + x (u32), lt * 1024 + pixel}
   int32_t* live_pos;           // per local pixel: its list position, -1: not live
+  // an adaptive progression's add: per local pixel, nonzero while it is active, or null.
+  // A stopped pixel gets empty primary masks, so it is in no block's live bits and not in the live list.
+  const uint32_t* active;
+  // 1: the schedule has no primary culling of its own (rt_tuning.frustum = 0, or a scene without
+  // candidate masks): tile_masks then hold every primitive for every tile and a pixel's masks are its
+  // tile's, untested, so that they only carry the active flags
+  int32_t own_masks;
 };
 size_t sched_scratch_bytes(int local);
 void sched_layout(void* scratch, int local, SchedParams* p);
@@ -341,6 +348,30 @@ constexpr int kRendererPartitionSpp = 16;
 // d_out[0] = pixels of a, b (RGBA8, npix each) that differ, d_out[1] = the
 // largest byte difference; zeroes d_out on the stream first (rt_rgba_delta_async)
 int launch_rgba_delta(const uint8_t* d_a, const uint8_t* d_b, size_t npix, uint32_t* d_out, void* stream);
+// ---- adaptive progressions
+// The per-pixel state of an adaptive progression, one word per local pixel
+// (lt * 1024 + pixel) each, and what adaptive_update_kernel needs to apply the
+// stop rule (include/rt_adaptive.h) after an add of n samples and to write the
+// image of every pixel of the rank's tiles.
+struct AdaptParams {
+  const double* acc;           // the progression's running sums (KParams::acc layout)
+  uint32_t* count;             // samples in the pixel's sum
+  uint32_t* streak;            // adds in a row within the tolerance
+  uint32_t* active;            // nonzero: still sampled
+  uint32_t* rgba;              // its displayed pixel after the last add that rendered it
+  unsigned long long* totals;  // [0] += active pixels after this add, [1] += sum of counts (zeroed before)
+  const int32_t* tile_list;    // per local tile: its global tile, or null: rank + lt * world
+  float* out_linear;           // the add's image (either may be null), laid out by `layout`
+  uint8_t* out_rgba;
+  int32_t npix, n;             // local pixels (local tiles * 1024); samples this add gave every active pixel
+  int32_t W, H, rank, world, tiles_x, ntiles, layout;
+  int32_t tolerance, patience, min_samples;
+};
+int launch_adaptive_update(const AdaptParams& p, void* stream);
+// The counts laid out for the caller (rt_context_progressive_counts_async):
+// count null: every in-image pixel gets `uniform`.  IMAGE layout: d_out (W*H
+// words) is zeroed on the stream first.
+int launch_progressive_counts(const AdaptParams& p, uint32_t uniform, uint32_t* d_out, void* stream);
 int launch_unpack(int32_t W, int32_t H, int32_t world, const void* gathered, size_t share_bytes, size_t rgba_off,
                   float* ol, uint8_t* orgba, void* stream);
 // The same for a partition: slot[t] = {owner rank, local tile} of global tile t;
@@ -454,7 +485,12 @@ struct WfParams {
 // class k, event k + 1 closes it; a skipped kernel takes no time).
 enum { kWfExtend = 0, kWfShade1, kWfHard, kWfCone, kWfSoftgen, kWfList, kWfSoft, kWfShade, kWfRegen, kWfResolve, kWfClasses };
 constexpr int kWfProfEvents = kWfClasses + 1;  // (one block serves any class range)
-int wf_launch_bounce(const WfParams& p, bool first, bool count, void* stream, const void* prof);
+// active (an adaptive progression's add; null: every pixel
+// renders): per local pixel, nonzero while it is active -- the samples of a
+// stopped pixel become dead slots (wf_regen_active, a kernel of its own: the
+// kernels of a plain frame take WfParams alone, as they were).
+int wf_launch_bounce(const WfParams& p, bool first, bool count, void* stream, const void* prof,
+                     const uint32_t* active = nullptr);
 // Quantized nodes the traversal kernels can stage in LDS next to their stacks
 // (all of them when they fit; else an odd count, so no child pair is split).
 // Load each kernel file's code object onto the current device (HIP loads

@@ -119,6 +119,10 @@ __device__ __forceinline__ void put_u64(int32_t* r, unsigned long long v) {
 }
 
 // K1: one wave per 64 pixels of a local tile.
+// (kAdaptive, here and in sched_est and sched_live: the schedule of an adaptive
+// progression's add, DESIGN.md §4.10 -- instantiations of their own, so that the
+// kernels of every other schedule stay the code they were)
+template <bool kAdaptive>
 __global__ __launch_bounds__(64) void sched_pixels(const SchedParams p) {
   const int lt = blockIdx.x >> 4, w = blockIdx.x & 15, lane = threadIdx.x;
   const int q = w * 64 + lane, t = p.tile_list ? p.tile_list[lt] : p.rank + lt * p.world;
@@ -126,7 +130,19 @@ __global__ __launch_bounds__(64) void sched_pixels(const SchedParams p) {
   if (p.tile_masks) {
     const unsigned long long ts = p.tile_masks[2 * lt], tt = p.tile_masks[2 * lt + 1];
     const int x = (t % p.tiles_x) * 32 + (q & 31), y = (t / p.tiles_x) * 32 + (q >> 5);
-    if (t < p.ntiles && (ts | tt) && x < p.W && y < p.H) {
+    // (an adaptive add, DESIGN.md §4.10: a stopped pixel keeps empty masks, so it is in no block's
+    // live bits and not in the live list -- its samples are not traced and its sum gets +0)
+    bool sampled = true, own = false;
+    if constexpr (kAdaptive) {
+      sampled = p.active[(size_t)lt * 1024 + q] != 0u;
+      own = p.own_masks != 0;
+    }
+    if (kAdaptive && own) {
+      if (t < p.ntiles && x < p.W && y < p.H && sampled) {
+        ms = ts;  // no primary culling of its own: the tile's (every primitive), untested
+        mt = tt;
+      }
+    } else if (t < p.ntiles && (ts | tt) && x < p.W && y < p.H && sampled) {
       double axis[3], cmin, smax;
       pixel_cone(p.cf, p.W, p.H, x, y, axis, &cmin, &smax);
       for (unsigned long long b = ts; b; b &= b - 1) {
@@ -163,6 +179,7 @@ __global__ __launch_bounds__(64) void sched_pixels(const SchedParams p) {
 }
 
 // K2: per pixel, the estimated path work of one sample.
+template <bool kAdaptive>
 __global__ __launch_bounds__(256) void sched_est(const SchedParams p) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)p.local * 1024) return;
@@ -192,6 +209,12 @@ __global__ __launch_bounds__(256) void sched_est(const SchedParams p) {
   } else {  // no pilot: every pixel of a tile with geometry weighs half a block
     const float c = p.tile_cost[lt];
     e = c > 0 ? (float)(p.block_work / (2.0 * max(1, p.spp))) * (1.0f + 1e-3f * fminf(c, 100.0f)) : 0.0f;
+  }
+  if constexpr (kAdaptive) {
+    if (p.active[i] == 0u) {  // a stopped pixel of an adaptive add: nothing to trace
+      e = 0.0f;
+      heavy = false;
+    }
   }
   // the sign bit marks a pixel to split (est >= 0 otherwise)
   p.est[i] = heavy ? -e - 1e-30f : e;
@@ -425,7 +448,7 @@ __global__ __launch_bounds__(64) void sched_tile_work(const SchedParams p, float
 // totals[3], pass 2 writes each pixel at its class's cursor.  Counts per
 // workgroup in LDS, one global atomic per class and workgroup.  The order
 // inside a class follows the atomics; the image does not depend on it.
-template <bool kWrite>
+template <bool kWrite, bool kAdaptive>
 __global__ __launch_bounds__(256) void sched_live(const SchedParams p) {
   __shared__ int s_cnt[kBuckets], s_base[kBuckets];
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -439,7 +462,7 @@ __global__ __launch_bounds__(256) void sched_live(const SchedParams p) {
     x = (t % p.tiles_x) * 32 + (q & 31);
     y = (t / p.tiles_x) * 32 + (q >> 5);
     live = t < p.ntiles && x < p.W && y < p.H &&
-           (!(p.frustum && p.tile_masks) || (p.pixmask[i * 2] | p.pixmask[i * 2 + 1]) != 0);
+           (!((p.frustum || kAdaptive) && p.tile_masks) || (p.pixmask[i * 2] | p.pixmask[i * 2 + 1]) != 0);
     if (live) {
       b = bucket_of((double)fabsf(p.est[i]) * 64.0);
       r = atomicAdd(&s_cnt[b], 1);
@@ -487,10 +510,12 @@ int sched_launch_live(const SchedParams& p, bool write, void* stream) {
   if (!write) {
     const hipError_t e = hipMemsetAsync(p.live_hist, 0, kBuckets * sizeof(int32_t), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((sched_live<false>), dim3(n), dim3(256), 0, s, p);
+    if (p.active) hipLaunchKernelGGL((sched_live<false, true>), dim3(n), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((sched_live<false, false>), dim3(n), dim3(256), 0, s, p);
     hipLaunchKernelGGL(sched_live_scan, dim3(1), dim3(kBuckets), 0, s, p);
   } else {
-    hipLaunchKernelGGL((sched_live<true>), dim3(n), dim3(256), 0, s, p);
+    if (p.active) hipLaunchKernelGGL((sched_live<true, true>), dim3(n), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((sched_live<true, false>), dim3(n), dim3(256), 0, s, p);
   }
   return (int)hipGetLastError();
 }
@@ -499,7 +524,7 @@ int sched_launch_tile_work(const SchedParams& p, float* tile_work, void* stream)
   hipStream_t s = (hipStream_t)stream;
   if (p.local <= 0) return hipSuccess;
   const unsigned n = (unsigned)(((size_t)p.local * 1024 + 255) / 256);
-  hipLaunchKernelGGL(sched_est, dim3(n), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(sched_est<false>, dim3(n), dim3(256), 0, s, p);
   hipLaunchKernelGGL(sched_tile_work, dim3(p.local), dim3(64), 0, s, p, tile_work);
   return (int)hipGetLastError();
 }
@@ -529,7 +554,7 @@ void sched_layout(void* scratch, int local, SchedParams* p) {
 // (see preload_render_kernels)
 int preload_sched_kernels() {
   hipFuncAttributes a;
-  return (int)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(sched_est));
+  return (int)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(sched_est<false>));
 }
 
 int sched_launch_pixels(const SchedParams& p, void* stream) {
@@ -537,7 +562,8 @@ int sched_launch_pixels(const SchedParams& p, void* stream) {
   if (p.local <= 0) return hipSuccess;
   const hipError_t e = hipMemsetAsync(p.hist, 0, (2 * kBuckets + 4) * sizeof(int32_t), s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sched_pixels, dim3(p.local * 16), dim3(64), 0, s, p);
+  if (p.active) hipLaunchKernelGGL(sched_pixels<true>, dim3(p.local * 16), dim3(64), 0, s, p);
+  else hipLaunchKernelGGL(sched_pixels<false>, dim3(p.local * 16), dim3(64), 0, s, p);
   return (int)hipGetLastError();
 }
 
@@ -546,7 +572,8 @@ int sched_launch_blocks(const SchedParams& p, bool write, void* stream) {
   if (p.local <= 0) return hipSuccess;
   if (!write) {
     const unsigned n = (unsigned)(((size_t)p.local * 1024 + 255) / 256);
-    hipLaunchKernelGGL(sched_est, dim3(n), dim3(256), 0, s, p);
+    if (p.active) hipLaunchKernelGGL(sched_est<true>, dim3(n), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(sched_est<false>, dim3(n), dim3(256), 0, s, p);
     hipLaunchKernelGGL((sched_blocks<false>), dim3(p.local), dim3(64), 0, s, p);
     hipLaunchKernelGGL(sched_scan, dim3(1), dim3(kBuckets), 0, s, p);
   } else {

@@ -1578,8 +1578,12 @@ __device__ __forceinline__ RegenPlan regen_plan(const WfCtl* ctl, int shard_cap)
   return r;
 }
 
-template <bool kCount>
-__global__ __launch_bounds__(kWfBlock) void wf_regen(const WfParams p) {
+// kActive (an adaptive progression's add; wf_regen_active, a
+// kernel of its own): the samples of a pixel that has stopped (active[local
+// pixel] == 0) are dead slots too, so its radiance rows stay +0 and
+// wf_resolve leaves its sum as it is.
+template <bool kCount, bool kActive>
+__device__ __forceinline__ void regen_body(const WfParams& p, const uint32_t* __restrict__ active) {
   const int t = blockIdx.x * kWfBlock + threadIdx.x;  // over kWfShards * shard_cap slots
   const int s = min(t / p.shard_cap, kWfShards - 1), local = t - s * p.shard_cap;
   const int have = p.ctl->next_cnt[s * 32];
@@ -1606,7 +1610,9 @@ __global__ __launch_bounds__(kWfBlock) void wf_regen(const WfParams p) {
       const int tile = p.tile_list ? p.tile_list[lt] : p.rank + lt * p.world;
       const int x = (tile % p.tiles_x) * 32 + (tp & 31), y = (tile / p.tiles_x) * 32 + (tp >> 5);
       const size_t slot = (size_t)s * p.shard_cap + local;
-      if (tile >= p.ntiles || x >= p.W || y >= p.H) {
+      bool dead = tile >= p.ntiles || x >= p.W || y >= p.H;
+      if constexpr (kActive) dead = dead || active[lp] == 0u;
+      if (dead) {
         p.next.sid[slot] = kDeadSid;
       } else {
         cnt<kCount>(c, C_CAM);
@@ -1619,6 +1625,14 @@ __global__ __launch_bounds__(kWfBlock) void wf_regen(const WfParams p) {
     }
   }
   flush_counts<kCount>(p, c);
+}
+template <bool kCount>
+__global__ __launch_bounds__(kWfBlock) void wf_regen(const WfParams p) {
+  regen_body<kCount, false>(p, nullptr);
+}
+template <bool kCount>
+__global__ __launch_bounds__(kWfBlock) void wf_regen_active(const WfParams p, const uint32_t* active) {
+  regen_body<kCount, true>(p, active);
 }
 
 // ---------------------------------------------------------------- book
@@ -1727,10 +1741,12 @@ static inline void mark(const hipEvent_t* ev, int k, hipStream_t st) {
 }
 
 template <bool kCount>
-static int enqueue_regen_book(const WfParams& p, hipStream_t st, const hipEvent_t* ev) {
+static int enqueue_regen_book(const WfParams& p, hipStream_t st, const hipEvent_t* ev, const uint32_t* active) {
   const int slots = kWfShards * p.shard_cap;
   // (once every sample has started, regen has nothing to do)
-  if (!p.dry) hipLaunchKernelGGL((wf_regen<kCount>), dim3((slots + kWfBlock - 1) / kWfBlock), dim3(kWfBlock), 0, st, p);
+  const dim3 rg((slots + kWfBlock - 1) / kWfBlock), rb(kWfBlock);
+  if (!p.dry && active) hipLaunchKernelGGL((wf_regen_active<kCount>), rg, rb, 0, st, p, active);
+  else if (!p.dry) hipLaunchKernelGGL((wf_regen<kCount>), rg, rb, 0, st, p);
   hipLaunchKernelGGL(wf_book, dim3(1), dim3(64), 0, st, p);
   mark(ev, kWfRegen + 1, st);
   return (int)hipGetLastError();
@@ -1798,7 +1814,7 @@ static void enqueue_trav(const WfParams& p, hipStream_t st, int which) {
 }
 
 template <bool kCount>
-static int enqueue_bounce(const WfParams& p, hipStream_t st, const hipEvent_t* ev) {
+static int enqueue_bounce(const WfParams& p, hipStream_t st, const hipEvent_t* ev, const uint32_t* active) {
   const dim3 b(kWfBlock);
   // dense kernels: one thread per live path, at most one per slot; while the
   // last paths drain, the host's bound keeps tens of thousands of empty
@@ -1838,18 +1854,19 @@ static int enqueue_bounce(const WfParams& p, hipStream_t st, const hipEvent_t* e
   mark(ev, kWfShade, st);
   hipLaunchKernelGGL((wf_shade<kCount>), gd, b, 0, st, p);
   mark(ev, kWfRegen, st);
-  return enqueue_regen_book<kCount>(p, st, ev);
+  return enqueue_regen_book<kCount>(p, st, ev, active);
 }
 
 // first == true: the arrays are empty; only regen + book (the first samples)
-int wf_launch_bounce(const WfParams& p, bool first, bool count, void* stream, const void* prof) {
+int wf_launch_bounce(const WfParams& p, bool first, bool count, void* stream, const void* prof,
+                     const uint32_t* active) {
   hipStream_t st = (hipStream_t)stream;
   const hipEvent_t* ev = (const hipEvent_t*)prof;
   if (first) {
     mark(ev, kWfRegen, st);
-    return count ? enqueue_regen_book<true>(p, st, ev) : enqueue_regen_book<false>(p, st, ev);
+    return count ? enqueue_regen_book<true>(p, st, ev, active) : enqueue_regen_book<false>(p, st, ev, active);
   }
-  return count ? enqueue_bounce<true>(p, st, ev) : enqueue_bounce<false>(p, st, ev);
+  return count ? enqueue_bounce<true>(p, st, ev, active) : enqueue_bounce<false>(p, st, ev, active);
 }
 
 // (see preload_render_kernels)

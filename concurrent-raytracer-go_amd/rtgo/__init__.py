@@ -199,6 +199,17 @@ COUNT_FIELDS = [
 ]
 
 
+class Adaptive(ctypes.Structure):
+    """rt_adaptive: the stop rule of an adaptive progression."""
+
+    _fields_ = [
+        ("tolerance", ctypes.c_int32),
+        ("patience", ctypes.c_int32),
+        ("min_samples", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+    ]
+
+
 class Counts(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in COUNT_FIELDS] + [("culled", ctypes.c_uint64 * 9),
                                                                ("soft_occlusion", ctypes.c_uint64 * 9),
@@ -300,6 +311,10 @@ EXPORTED_SYMBOLS = [
     "rt_context_progressive_samples",
     "rt_context_progressive_end",
     "rt_rgba_delta_async",
+    "rt_context_progressive_set_adaptive",
+    "rt_context_progressive_counts_async",
+    "rt_context_progressive_state",
+    "rt_adaptive_step",
 ]
 
 _lib = None
@@ -408,6 +423,11 @@ def lib():
         "rt_context_progressive_samples": (ctypes.c_int64, [vp]),
         "rt_context_progressive_end": (ctypes.c_int, [vp]),
         "rt_rgba_delta_async": (ctypes.c_int, [vp, vp, sz, vp, vp]),
+        "rt_context_progressive_set_adaptive": (ctypes.c_int, [vp, ctypes.POINTER(Adaptive)]),
+        "rt_context_progressive_counts_async": (ctypes.c_int, [vp, vp, vp]),
+        "rt_context_progressive_state": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
+        "rt_adaptive_step": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), i32, i32,
+                                             i32, ctypes.POINTER(Adaptive), ctypes.POINTER(i32)]),
         "rt_camera_frame": (ctypes.c_int, [ctypes.POINTER(Camera), i32, i32, i32, ctypes.POINTER(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -558,6 +578,8 @@ class ParallelRenderer:
         self._tuning = None
         self.last_samples = None  # samples per pixel of the last render_progressive
         self._prog_ctx = None  # its Context (made by the first call, kept)
+        self.last_sample_counts = None  # per-pixel samples of the last render_progressive (H x W)
+        self.last_progressive_state = None  # Context.progressive_state() at its end
 
     def set_tuning(self, tuning: Tuning):
         self._tuning = tuning
@@ -685,7 +707,7 @@ class ParallelRenderer:
         return rgba
 
     def render_progressive(self, scene: Scene, width: int, height: int, pass_samples: int, time_budget=None,
-                           until_changed_pixels=None, on_pass=None) -> np.ndarray:
+                           until_changed_pixels=None, on_pass=None, adaptive=None) -> np.ndarray:
         """Render the frame ``pass_samples`` samples at a time, on one device.
 
         ``self.settings.samples`` is the cap; the last pass is clipped to it.
@@ -698,6 +720,14 @@ class ParallelRenderer:
         after n samples is that of ``render`` with samples = n, byte for byte.
         Returns the last image; ``last_linear`` holds its linear radiance and
         ``last_samples`` the samples rendered.
+
+        ``adaptive``: None, or a dict with ``tolerance`` and
+        optionally ``patience`` (1) and ``min_samples`` (0): every pixel stops
+        on its own (Context.progressive_set_adaptive), and the progression
+        also stops once no pixel is active.  Pixel p of the image is then that
+        of ``render`` with samples = ``last_sample_counts[p]``.  In every mode
+        ``last_sample_counts`` (H x W uint32) and ``last_progressive_state``
+        (Context.progressive_state) are set.
         """
         t0 = time.perf_counter()
         if (len(self.devices) if self.devices else max(1, self.settings.num_devices)) > 1:
@@ -720,8 +750,12 @@ class ParallelRenderer:
             lin = torch.zeros(npix * 3, dtype=torch.float32, device="cuda")
             bufs = [torch.zeros(npix * 4, dtype=torch.uint8, device="cuda") for _ in range(2)]
             delta = torch.zeros(2, dtype=torch.int32, device="cuda")
+            counts = torch.zeros(npix, dtype=torch.int32, device="cuda")
             ctx.progressive_begin(width, height, self.settings)
-            done, k, img = 0, 0, None
+            if adaptive is not None:
+                ctx.progressive_set_adaptive(adaptive["tolerance"], adaptive.get("patience", 1),
+                                             adaptive.get("min_samples", 0))
+            done, k, img, state = 0, 0, None, None
             try:
                 while True:
                     n = min(int(pass_samples), cap - done)
@@ -736,15 +770,24 @@ class ParallelRenderer:
                     if on_pass is not None:
                         on_pass(done, img, changed)
                     k += 1
+                    if adaptive is not None:
+                        state = ctx.progressive_state()
+                        if state["active"] == 0:
+                            break
                     if done >= cap:
                         break
                     if time_budget is not None and time.perf_counter() - t0 >= time_budget:
                         break
                     if until_changed_pixels is not None and changed is not None and changed <= until_changed_pixels:
                         break
+                state = ctx.progressive_state()
+                ctx.progressive_counts(counts.data_ptr(), 0)
+                torch.cuda.synchronize()
             finally:
                 ctx.progressive_end()
             self.last_linear = lin.cpu().numpy().reshape(height, width, 3)
+            self.last_sample_counts = counts.cpu().numpy().view(np.uint32).reshape(height, width)
+        self.last_progressive_state = state
         self.last_samples = done
         self.benchmark_data = {
             "scene_name": "demo_scene",
@@ -756,6 +799,7 @@ class ParallelRenderer:
             "timestamp": datetime.now(timezone.utc).isoformat(),
             "features": list(self.FEATURES),
             "passes": k,
+            "mean_samples_per_pixel": state["samples"] / max(1, state["pixels"]),
         }
         return img
 
@@ -841,6 +885,28 @@ class Context:
         image of the mean over all samples so far into d_linear / d_rgba (either may be 0)."""
         _check(lib().rt_context_progressive_add_async(self._h, nsamples, ctypes.c_void_p(d_linear),
                                                        ctypes.c_void_p(d_rgba), ctypes.c_void_p(stream)))
+
+    def progressive_set_adaptive(self, tolerance, patience: int = 1, min_samples: int = 0):
+        """rt_context_progressive_set_adaptive: after progressive_begin and before the first add, every
+        pixel stops on its own once its displayed RGBA8 moved by at most `tolerance` for `patience` adds in
+        a row and it has at least `min_samples` samples.  tolerance=None switches it off again."""
+        if tolerance is None:
+            _check(lib().rt_context_progressive_set_adaptive(self._h, None))
+            return
+        a = Adaptive(int(tolerance), int(patience), int(min_samples), 0)
+        _check(lib().rt_context_progressive_set_adaptive(self._h, ctypes.byref(a)))
+
+    def progressive_counts(self, d_counts: int, stream: int = 0):
+        """rt_context_progressive_counts_async: the per-pixel sample counts (uint32) in the progression's
+        layout into the device buffer d_counts."""
+        _check(lib().rt_context_progressive_counts_async(self._h, ctypes.c_void_p(d_counts), ctypes.c_void_p(stream)))
+
+    def progressive_state(self) -> dict:
+        """rt_context_progressive_state (waits for the last add): in-image pixels of the rank's tiles, those
+        still active, the sum of their sample counts, adds so far."""
+        out = (ctypes.c_int64 * 4)()
+        _check(lib().rt_context_progressive_state(self._h, out))
+        return {"pixels": int(out[0]), "active": int(out[1]), "samples": int(out[2]), "adds": int(out[3])}
 
     def progressive_samples(self) -> int:
         """Samples per pixel the progression has rendered; -1: no progression."""
@@ -940,6 +1006,21 @@ def render(scene: Scene, width: int, height: int, settings: Settings):
     _check(lib().rt_render(ctypes.byref(scene.view), width, height, ctypes.byref(settings), lin.ctypes.data,
                            rgba.ctypes.data, ctypes.byref(st)))
     return rgba, lin, st
+
+
+def adaptive_step(old_rgba, new_rgba, had_image, count: int, streak: int, tolerance: int, patience: int = 1,
+                  min_samples: int = 0):
+    """rt_adaptive_step: the stop rule of an adaptive progression for one pixel on the host (no device):
+    (stop, new_streak) from its displayed RGBA before and after an add (four bytes each), whether it had an
+    image before the add, its sample count including the add and its streak before it."""
+    o = (ctypes.c_uint8 * 4)(*[int(v) for v in old_rgba])
+    n = (ctypes.c_uint8 * 4)(*[int(v) for v in new_rgba])
+    a = Adaptive(int(tolerance), int(patience), int(min_samples), 0)
+    ns = ctypes.c_int32(0)
+    rc = lib().rt_adaptive_step(o, n, 1 if had_image else 0, int(count), int(streak), ctypes.byref(a), ctypes.byref(ns))
+    if rc < 0:
+        _check(rc)
+    return bool(rc), int(ns.value)
 
 
 def rgba_delta_async(d_a: int, d_b: int, npix: int, d_out: int, stream: int = 0):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame; 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -457,6 +457,45 @@ int rt_context_progressive_add_async(rt_context* ctx, int32_t nsamples, float* d
                                      void* hip_stream);
 int64_t rt_context_progressive_samples(const rt_context* ctx);
 int rt_context_progressive_end(rt_context* ctx);
+
+/* Adaptive sampling: every pixel of a progression stops on
+ * its own once its displayed value has stopped moving.  Each in-image pixel
+ * of the rank's tiles has a sample count, a streak and an active flag
+ * (initially set).  An adaptive add of n samples renders samples [count,
+ * count + n) of every ACTIVE pixel (all active pixels share count == the
+ * samples done), continues its sum in sample order, and then, per active
+ * pixel: new = the tone-mapped RGBA8 of (float)(sum / count); when the pixel
+ * had an image before this add, d = the largest |new - old| over the four
+ * bytes and streak = d <= tolerance ? streak + 1 : 0 (on the first add the
+ * streak stays 0); the pixel stops for good when streak >= patience and
+ * count >= min_samples, keeping its sum, count and image.  A stopped pixel is
+ * neither traced nor changed by later adds.  After every add d_linear /
+ * d_rgba hold (float)(sum / count) and its tone map for EVERY pixel, stopped
+ * ones included: pixel p is that of rt_context_render_async with samples =
+ * count[p], byte for byte.  The rule reads no neighbour, so image and counts
+ * are the same for every partition, rank count, path and tuning. */
+typedef struct { int32_t tolerance, patience, min_samples, _pad; } rt_adaptive;
+/* After rt_context_progressive_begin and before its first add; NULL: off (the
+ * default after every begin).  RT_E_INVALID (nothing changes) without a
+ * progression, after an add, for tolerance outside 0..255, patience < 1,
+ * min_samples < 0, and for a progression with a sky (its images match the
+ * reference only to a tolerance, so its stop decisions could not be pinned). */
+int rt_context_progressive_set_adaptive(rt_context* ctx, const rt_adaptive* a);
+/* Per-pixel sample counts in the progression's layout (IMAGE: W*H words,
+ * pixels outside this rank's tiles 0; PACKED: local tiles * 1024 words, pixels
+ * outside the image 0), a device pointer, on `hip_stream` after the last add.
+ * Without set_adaptive every pixel's count is the samples done. */
+int rt_context_progressive_counts_async(rt_context* ctx, uint32_t* d_counts, void* hip_stream);
+/* Waits for the last add.  out = in-image pixels of the rank's tiles, those of
+ * them still active, the sum of their counts, adds so far. */
+int rt_context_progressive_state(rt_context* ctx, int64_t out[4]);
+/* The stop rule for one pixel on the host (the function the device kernel
+ * applies, include/rt_adaptive.h): old / new displayed RGBA, whether the pixel
+ * had an image before the add, its count including the add, its streak before
+ * it.  Returns 1 stop, 0 go on, with *new_streak set; RT_E_INVALID on NULL
+ * arguments or values out of range (a as for set_adaptive, count or streak < 0). */
+int rt_adaptive_step(const uint8_t old_rgba[4], const uint8_t new_rgba[4], int32_t had_image, int32_t count,
+                     int32_t streak, const rt_adaptive* a, int32_t* new_streak);
 /* How much two RGBA8 images of npix pixels (device pointers) differ, into the
  * two device words d_out: [0] the pixels whose four bytes are not all equal,
  * [1] the largest |a - b| over all bytes.  Zeroes d_out on the stream first.
