@@ -636,7 +636,7 @@ __device__ __forceinline__ void camera_ray_c(const CamK& ck, const Frame& f, int
   }
 }
 
-// `f` lives in the kernel arguments (camera_frame, rt_api.cpp).  The
+// `f` lives in the kernel arguments (camera_frame, scene_flat.cpp).  The
 // reference model keeps forming its corner here from the origin and vw, the
 // three operations the kernels have always executed (the host's frame holds
 // the same bits): loading it instead changed the register allocation of the

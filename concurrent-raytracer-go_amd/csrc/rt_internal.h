@@ -1,5 +1,5 @@
-// rt_internal.h — host-side interfaces between the C ABI (rt_api.cpp), the
-// kernels (rt_kernel.hip), the scene loader (scene_json.cpp), the BVH
+// rt_internal.h — host-side interfaces between the C ABI (rt_api.cpp and the
+// files around rt_context.h), the kernels (rt_kernel.hip), the scene loader (scene_json.cpp), the BVH
 // builder (bvh.cpp) and the output writers (image_io.cpp).
 #pragma once
 #include <stdint.h>
@@ -341,7 +341,7 @@ int launch_download(const void* d_src, void* h_dst_mapped, size_t bytes, void* s
 // renderer watchdog's test hook, rt_multi.cpp test_stall)
 int launch_spin(double ms, void* stream);
 // rt_partition_balanced measuring only the first measure_spp samples of every
-// pixel (rt_api.cpp measured_tile_work; the renderer's partitions: 16)
+// pixel (rt_partition.cpp measured_tile_work; the renderer's partitions: 16)
 int partition_balanced(rt_context* c, int32_t w, int32_t h, const rt_settings* st, int32_t world, int measure_spp,
                        rt_partition** out);
 constexpr int kRendererPartitionSpp = 16;

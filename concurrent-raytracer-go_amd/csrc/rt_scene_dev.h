@@ -1,6 +1,6 @@
 // rt_scene_dev.h — flattened, device-resident scene layout (HBM).
 //
-// Produced on the host by flatten_scene() (rt_api.cpp) from the boundary's
+// Produced on the host by flatten_scene() (scene_flat.cpp) from the boundary's
 // rt_scene (objects-level, like scene.Scene, internal/scene/scene.go:12-16)
 // and read by the gfx950 kernels (rt_kernel.hip).  Everything the reference
 // recomputes per test but which depends only on the scene is precomputed

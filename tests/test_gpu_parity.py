@@ -151,7 +151,7 @@ def test_opt_in_sky_on_the_wavefront_path():
                                        1501)], ids=["spheres_2100spp", "silver_1501spp"])
 def test_sample_passes_match_oracle(case, spp):
     """More samples per pixel than a block holds (1024) render as sample
-    passes that continue every pixel's running sum (rt_api.cpp,
+    passes that continue every pixel's running sum (rt_render.cpp,
     KParams.acc): SetSamples takes any count in the reference
     (settings.go:3-5), and the image is still tracePixel's sum in sample
     order, bit for bit.  1501 = 750 + 751: the passes differ in size, so the

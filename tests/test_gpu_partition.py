@@ -225,7 +225,7 @@ def test_frames_of_one_launch_equal_single_renders(tuning):
     of 3 ranks of a balanced partition, 4 frames per launch, gathered as
     [rank][frame][share] and unpacked in one launch.  With the default tuning
     the launch of 6 frames is cut into larger blocks than a single render's
-    (1024 vs 384 bounce-samples, rt_api.cpp default_block_work), so this also
+    (1024 vs 384 bounce-samples, rt_render.cpp default_block_work), so this also
     checks that the image does not depend on the schedule."""
     import torch
 
@@ -274,7 +274,7 @@ def test_frames_of_one_launch_equal_single_renders(tuning):
 def test_batched_triangle_frames_equal_single_renders():
     """The silver prism / purple cube scene (BASELINE C3: triangles, the
     batched schedule cuts 2048 bounce-samples per block against 256 for one
-    frame, rt_api.cpp default_block_work): 3 frames of one launch, each
+    frame, rt_render.cpp default_block_work): 3 frames of one launch, each
     bit-identical to its own single render, whose parity with the oracle the
     full-size tests pin."""
     import torch

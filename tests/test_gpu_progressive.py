@@ -151,6 +151,16 @@ def test_sub_passes_inside_one_add():
     assert s["frames"] == 2 and s["launches"] == 3, s
 
 
+def test_sub_passes_of_an_add_never_stream():
+    """The same adds with the stream path forced: the 401-sample add is one
+    launch and streams; the 1100-sample add's last sub-pass has the acc_mode of
+    a one-launch add, yet both of its sub-passes take the block kernel."""
+    p = _run(("file", "final_silver_prism_purple_cube_facing.json"), 20, 14, {}, 6, [401, 1100], tun={"stream": 1})
+    s = p.stats()
+    p.close()
+    assert s["frames"] == 2 and s["launches"] == 3 and s["stream_launches"] == 1, s
+
+
 # ---------------------------------------------------------------- 3. stream path
 def test_stream_path_continues_the_sum_and_reuses_the_schedule():
     over = {"max_depth": 12}

@@ -1,7 +1,7 @@
 """GPU: the image does not depend on how the work is cut and ordered.
 
 The host cuts a rank's tiles into work blocks from a one-sample pilot render
-(rt_api.cpp prepare_schedule, schedule.cpp build_blocks): blocks of several
+(rt_render.cpp prepare_schedule, schedule.cpp build_blocks): blocks of several
 pixels, single pixels, and pixels SPLIT into sample ranges that the last
 finishing range resolves.  Every schedule must give the oracle's image bit
 for bit.  The rt_tuning settings below force each kind of block.

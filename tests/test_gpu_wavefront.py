@@ -125,7 +125,7 @@ def test_more_than_32_lights_match_the_oracle():
 def test_more_than_1024_samples_on_both_bvh_paths():
     """A sample count past one block's 1024 on a BVH scene: the wavefront
     path (no per-pixel limit) and the megakernel's BVH path (sample passes,
-    rt_api.cpp) both give the oracle's image."""
+    rt_render.cpp) both give the oracle's image."""
     scene = rtgo.Scene.from_json_text(json.dumps(_sphere_field(300, seed=8)))
     st = make_settings(rtgo, {"samples": 1100, "max_depth": 6}, seed=2)
     w, h = 16, 12
