@@ -129,7 +129,10 @@ struct rt_context {
   int32_t tail_cap = 0, tail_spp = -1;  // the layout of d.tail
   uint32_t tail_epoch = 0;
   int32_t nlive = -1, live_local = 0;  // d.live's pixels (nlive < 0: this schedule has none)
-  int32_t wave_slots = 0;  // resident waves of render_stream_kernel on this device (its grid)
+  // per stream kernel (stream_kernel_of): its resident waves on this device
+  // (its grid) at wave_shmem bytes of dynamic LDS, as the runtime reports them
+  int32_t wave_slots[rtgo::kStreamKernels] = {0};
+  size_t wave_shmem[rtgo::kStreamKernels] = {0};
   // a progression: its frame (prog_st.samples: the cap) and
   // the samples of every pixel done so far
   bool prog_on = false;

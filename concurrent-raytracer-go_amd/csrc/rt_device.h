@@ -343,12 +343,44 @@ struct HitSel {
   int is_tri;
 };
 
+// The same two for a scene of spheres alone (kSph: no triangle, no cube; the
+// spheres-only stream kernels): no triangle mask to carry and
+// shuffle, no barycentrics, no kind.  Kind<kSph> names the pair.
+struct CandS {
+  unsigned long long s;
+};
+struct HitSelS {
+  double num;
+  int idx;
+};
+template <bool kSph>
+struct Kind {
+  typedef Cand C;
+  typedef HitSel H;
+};
+template <>
+struct Kind<true> {
+  typedef CandS C;
+  typedef HitSelS H;
+};
+__device__ __forceinline__ bool hit_is_tri(const HitSel& h) { return h.is_tri != 0; }
+__device__ __forceinline__ bool hit_is_tri(const HitSelS&) { return false; }
+__device__ __forceinline__ bool cand_any(Cand m) { return (m.s | m.t) != 0; }
+__device__ __forceinline__ bool cand_any(CandS m) { return m.s != 0; }
+template <bool kSph>
+__device__ __forceinline__ typename Kind<kSph>::C cand_all() {  // every primitive
+  typename Kind<kSph>::C m{};
+  m.s = ~0ull;
+  if constexpr (!kSph) m.t = ~0ull;
+  return m;
+}
+
 // hitWorld closest hit, renderer.go:333-346.  Linear scan in hittable order
 // (spheres before triangles; an exact-t tie is resolved by hittable index so
 // the later hittable wins, as in Go), or BVH traversal with the same rule.
-template <bool kCount>
-__device__ __forceinline__ bool closest_hit(const Geo& p, d3 o, d3 d, HitSel& hs, int* stack, Cand m,
-                                            Counters& c) {
+template <bool kCount, bool kSph = false>
+__device__ __forceinline__ bool closest_hit(const Geo& p, d3 o, d3 d, typename Kind<kSph>::H& hs, int* stack,
+                                            typename Kind<kSph>::C m, Counters& c) {
   const double tmin = 0.001;
   double closest = __builtin_inf();
   bool found = false;
@@ -397,7 +429,7 @@ __device__ __forceinline__ bool closest_hit(const Geo& p, d3 o, d3 d, HitSel& hs
           closest = t;
           hs.num = num;
           hs.idx = i;
-          hs.is_tri = 0;
+          if constexpr (!kSph) hs.is_tri = 0;
           best_obj = S.obj;
           found = true;
         }
@@ -420,33 +452,35 @@ __device__ __forceinline__ bool closest_hit(const Geo& p, d3 o, d3 d, HitSel& hs
       closest = t;
       hs.num = num;
       hs.idx = i;
-      hs.is_tri = 0;
+      if constexpr (!kSph) hs.is_tri = 0;
       best_obj = S.obj;
       found = true;
     }
   }
-  // triangles cube by cube, in hittable order: a cube whose box the ray
-  // misses within [tmin, closest] cannot hold an accepted hit
-  const d3 id = inv_dir(d);
-  for (int j = 0; j < p.nb; ++j) {
-    const DBox& B = p.boxes[j];
-    if (use_m && !((m.t >> B.first) & 0xFFFull)) continue;
-    if (!ray_box(B, o, id, tmin, closest)) continue;
-    for (int i = B.first; i < B.first + B.count; ++i) {
-      if (use_m && !((m.t >> i) & 1)) continue;
-      cnt<kCount>(c, C_TRI);
-      const DTri& T = p.tris[i];
-      double t, u, v;
-      if (tri_test(T, o, d, tmin, closest, t, u, v)) {
-        if (t == closest && best_obj > T.obj) continue;
-        closest = t;
-        hs.num = t;
-        hs.u = u;
-        hs.v = v;
-        hs.idx = i;
-        hs.is_tri = 1;
-        best_obj = T.obj;
-        found = true;
+  if constexpr (!kSph) {
+    // triangles cube by cube, in hittable order: a cube whose box the ray
+    // misses within [tmin, closest] cannot hold an accepted hit
+    const d3 id = inv_dir(d);
+    for (int j = 0; j < p.nb; ++j) {
+      const DBox& B = p.boxes[j];
+      if (use_m && !((m.t >> B.first) & 0xFFFull)) continue;
+      if (!ray_box(B, o, id, tmin, closest)) continue;
+      for (int i = B.first; i < B.first + B.count; ++i) {
+        if (use_m && !((m.t >> i) & 1)) continue;
+        cnt<kCount>(c, C_TRI);
+        const DTri& T = p.tris[i];
+        double t, u, v;
+        if (tri_test(T, o, d, tmin, closest, t, u, v)) {
+          if (t == closest && best_obj > T.obj) continue;
+          closest = t;
+          hs.num = t;
+          hs.u = u;
+          hs.v = v;
+          hs.idx = i;
+          hs.is_tri = 1;
+          best_obj = T.obj;
+          found = true;
+        }
       }
     }
   }

@@ -327,10 +327,15 @@ struct StreamKArgs {           // the kernels' one argument: KParams at offset 0
   KParams k;
   StreamParams s;
 };
-// render_stream_kernel on `wgs` one-wave workgroups (0: the device's resident
-// wave slots), then resolve_rows_kernel; the cursor is zeroed first.
+// The launch's stream kernel (stream_kernel_of: generic or spheres-only, each
+// with its sample_base twin) on `wgs` one-wave workgroups, then
+// resolve_rows_kernel; the cursor is zeroed first.
 int launch_stream(const KParams& p, const StreamParams& sp, int wgs, void* stream);
-int stream_wave_slots(int device);
+constexpr int kStreamKernels = 4;
+int stream_kernel_of(const KParams& p);
+// resident one-wave workgroups of stream kernel `kernel` with `shmem` bytes of
+// dynamic LDS on `device` (the runtime's occupancy x CUs; 0: no answer)
+int stream_wave_slots(int device, int kernel, size_t shmem);
 
 // Enqueue the render kernel; returns hipError_t as int.
 int launch_render(const KParams& p, bool count, void* stream);

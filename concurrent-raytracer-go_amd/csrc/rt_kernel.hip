@@ -46,6 +46,11 @@
 #ifndef RT_WAVES_PER_SIMD
 #define RT_WAVES_PER_SIMD 3
 #endif
+// ... of the spheres-only stream kernels (render_stream_sph_kernel): 4 fit
+// without scratch (128 VGPRs) and measured 5 % faster than 3
+#ifndef RT_STREAM_SPH_WAVES
+#define RT_STREAM_SPH_WAVES 4
+#endif
 // cooperative soft shadows when at most this many lanes need them (measured
 // best of 0/2/4/8 in round 1; 4 and 16 within noise in round 2)
 #ifndef RT_COOP_MAX
@@ -88,6 +93,13 @@ __device__ __forceinline__ int lane_now() {  // (one-wave workgroups: the lane i
   int l;
   asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
   return l;
+}
+// +0.0 through a volatile move, for the same reason: the constant is made
+// where it is used instead of being kept in a register pair through the loop
+__device__ __forceinline__ double zero_now() {
+  double z;
+  asm volatile("v_mov_b64 %0, 0" : "=v"(z));
+  return z;
 }
 // Set bits of a wave mask below the calling lane (v_mbcnt): no 64-bit
 // per-lane "below" mask has to stay live (it was spilled to scratch)
@@ -137,35 +149,43 @@ __device__ __forceinline__ bool in_cone(const double* cc, double r, d3 P, d3 ldi
 //           winds them inward, so FrontFace there means a hit from inside.
 __device__ __forceinline__ bool box_self_out(const DBox& B, bool front) { return (int)front == B.front_out; }
 
-__device__ __forceinline__ Cand cone_candidates(const Geo& p, d3 P, d3 N, bool front, int self, d3 ldir,
-                                                double ldist) {
+// (kSph, here and below: the scene is spheres alone, DESIGN.md §4.7 -- no
+// triangle or cube code, and the candidates are the sphere mask, Kind<kSph>)
+template <bool kSph = false>
+__device__ __forceinline__ typename Kind<kSph>::C cone_candidates(const Geo& p, d3 P, d3 N, bool front, int self,
+                                                                  d3 ldir, double ldist) {
   const bool leaves = dot(N, ldir) >= KC(0.1015);
   const bool sphere_out = front && leaves;
-  Cand m{0ull, 0ull};
+  typename Kind<kSph>::C m{};
   for (int i = 0; i < p.ns; ++i) {
     const DSphere& S = p.spheres[i];
     if (sphere_out && S.obj == self && S.r > 0) continue;
     if (in_cone(S.c, S.r, P, ldir, ldist)) m.s |= 1ull << i;
   }
-  // triangles by cube: one cone test against the bounding sphere of the
-  // cube's box admits its 12 triangles (their exact tests follow per ray)
-  for (int j = 0; j < p.nb; ++j) {
-    const DBox& B = p.boxes[j];
-    if (leaves && B.obj == self && box_self_out(B, front)) continue;
-    if (in_cone(B.bc, B.br, P, ldir, ldist)) m.t |= 0xFFFull << B.first;
+  if constexpr (!kSph) {
+    // triangles by cube: one cone test against the bounding sphere of the
+    // cube's box admits its 12 triangles (their exact tests follow per ray)
+    for (int j = 0; j < p.nb; ++j) {
+      const DBox& B = p.boxes[j];
+      if (leaves && B.obj == self && box_self_out(B, front)) continue;
+      if (in_cone(B.bc, B.br, P, ldir, ldist)) m.t |= 0xFFFull << B.first;
+    }
   }
   return m;
 }
 
 // hitWorld(shadowRay, 0.001, dist) restricted to the candidates.
-template <bool kCount>
-__device__ __forceinline__ bool any_hit_masked(const Geo& p, d3 o, d3 d, double tmax, Cand m, Counters& c) {
-  if (m.t) {  // a cube whose box the ray misses cannot be hit: drop its 12 triangles
-    const d3 id = inv_dir(d);
-    for (int j = 0; j < p.nb; ++j) {
-      const DBox& B = p.boxes[j];
-      const unsigned long long g = 0xFFFull << B.first;
-      if ((m.t & g) && !ray_box(B, o, id, 0.001, tmax)) m.t &= ~g;
+template <bool kCount, bool kSph = false>
+__device__ __forceinline__ bool any_hit_masked(const Geo& p, d3 o, d3 d, double tmax, typename Kind<kSph>::C m,
+                                               Counters& c) {
+  if constexpr (!kSph) {
+    if (m.t) {  // a cube whose box the ray misses cannot be hit: drop its 12 triangles
+      const d3 id = inv_dir(d);
+      for (int j = 0; j < p.nb; ++j) {
+        const DBox& B = p.boxes[j];
+        const unsigned long long g = 0xFFFull << B.first;
+        if ((m.t & g) && !ray_box(B, o, id, 0.001, tmax)) m.t &= ~g;
+      }
     }
   }
   if (m.s) {  // (most camera rays have no candidate at all)
@@ -178,20 +198,23 @@ __device__ __forceinline__ bool any_hit_masked(const Geo& p, d3 o, d3 d, double 
       if (sphere_query(p.spheres[i], o, d, a, inv_a, 0.001, tmax, num)) return true;
     }
   }
-  for (unsigned long long b = m.t; b; b &= b - 1) {
-    const int i = __builtin_ctzll(b);
-    cnt<kCount>(c, C_TRI);
-    double t, u, v;
-    if (tri_test(p.tris[i], o, d, 0.001, tmax, t, u, v)) return true;
+  if constexpr (!kSph) {
+    for (unsigned long long b = m.t; b; b &= b - 1) {
+      const int i = __builtin_ctzll(b);
+      cnt<kCount>(c, C_TRI);
+      double t, u, v;
+      if (tri_test(p.tris[i], o, d, 0.001, tmax, t, u, v)) return true;
+    }
   }
   return false;
 }
 
 // Occlusion of one shadow ray: candidates when culling is on, else all.
-template <bool kCount>
-__device__ __forceinline__ bool shadow_blocked(const Geo& p, bool masks, d3 o, d3 d, double tmax, Cand m,
-                                               int* stack, Counters& c) {
-  if (masks) return (m.s | m.t) != 0 && any_hit_masked<kCount>(p, o, d, tmax, m, c);
+// (kSph: any_hit's triangle loops fold away, hot() sets nt = nb = 0)
+template <bool kCount, bool kSph = false>
+__device__ __forceinline__ bool shadow_blocked(const Geo& p, bool masks, d3 o, d3 d, double tmax,
+                                               typename Kind<kSph>::C m, int* stack, Counters& c) {
+  if (masks) return cand_any(m) && any_hit_masked<kCount, kSph>(p, o, d, tmax, m, c);
   return any_hit<kCount>(p, o, d, tmax, stack, c);
 }
 
@@ -225,9 +248,9 @@ __device__ __forceinline__ int wide_groups(bool need, unsigned long long qmask, 
 // the current hit unless its index is larger).  Exact for finite rays; an
 // owner with a non-finite ray (or a = 0) is flagged in `fallback` and scans
 // on its own.  Returns found for owner lanes.
-template <bool kCount>
+template <bool kCount, bool kSph = false>
 __device__ __forceinline__ bool closest_wide(const Geo& g, bool need, unsigned long long qmask, int nq, d3 o, d3 d,
-                                             HitSel& hs, bool& fallback, Counters& c) {
+                                             typename Kind<kSph>::H& hs, bool& fallback, Counters& c) {
   __shared__ int owner_tab[16];
   const int lane = (int)(threadIdx.x & 63);
   int ow, k;
@@ -273,7 +296,7 @@ __device__ __forceinline__ bool closest_wide(const Geo& g, bool need, unsigned l
   fallback = need && !(__builtin_isfinite(o.x + o.y + o.z) && a > 0 && __builtin_isfinite(__shfl(a, lead)));
   hs.num = fnum;
   hs.idx = fidx;
-  hs.is_tri = 0;
+  if constexpr (!kSph) hs.is_tri = 0;
   return ffound != 0;
 }
 
@@ -336,9 +359,12 @@ struct CoopOut {
   int unocc;   // unoccluded rays
   int tries;   // rejection tries consumed
 };
-template <bool kCount>
-__device__ __forceinline__ CoopOut soft_coop(const Geo p, bool masks, bool trace, d3 P, d3 ldir, double ldist, Cand cm, uint64_t x,
-                             const uint64_t* jump, int* stack, Counters& c) {
+// the candidates of lane `ow`, wave-uniform
+__device__ __forceinline__ Cand cand_of_lane(Cand m, int ow) { return Cand{rl64(m.s, ow), rl64(m.t, ow)}; }
+__device__ __forceinline__ CandS cand_of_lane(CandS m, int ow) { return CandS{rl64(m.s, ow)}; }
+template <bool kCount, bool kSph = false>
+__device__ __forceinline__ CoopOut soft_coop(const Geo p, bool masks, bool trace, d3 P, d3 ldir, double ldist,
+                             typename Kind<kSph>::C cm, uint64_t x, const uint64_t* jump, int* stack, Counters& c) {
   const int lane = (int)(threadIdx.x & 63);
   int need = 16, unocc = 0, tries = 0;
   while (need > 0) {
@@ -355,8 +381,8 @@ __device__ __forceinline__ CoopOut soft_coop(const Geo p, bool masks, bool trace
     const int used = nch == need ? 64 - __clzll(chm) : 64;
     bool occ = false;
     if (chosen && trace)
-      occ = shadow_blocked<kCount>(p, masks, P, normalize(ldir + muls(unit_ball_point(o0, o1, o2), 0.1)), ldist, cm,
-                                   stack, c);
+      occ = shadow_blocked<kCount, kSph>(p, masks, P, normalize(ldir + muls(unit_ball_point(o0, o1, o2), 0.1)), ldist,
+                                         cm, stack, c);
     unocc += nch - __popcll(__ballot(chosen && occ));
     need -= nch;
     tries += used;
@@ -377,10 +403,10 @@ __device__ __forceinline__ CoopOut soft_coop(const Geo p, bool masks, bool trace
 // lanes; here the tries run alone and the rays run on full waves.  The
 // result is a count of unoccluded rays, so the order in which rays are
 // traced does not change it.  Returns the owner's count (0 elsewhere).
-template <bool kCount>
+template <bool kCount, bool kSph = false>
 __device__ __forceinline__ int soft_queue(const Geo& p, bool masks, bool need_soft, bool trace, d3 P, d3 ldir,
-                                          double ldist, Cand cm, rt_rng& rng, const uint64_t* jump, int* stack,
-                                          Counters& c) {
+                                          double ldist, typename Kind<kSph>::C cm, rt_rng& rng, const uint64_t* jump,
+                                          int* stack, Counters& c) {
   // queued points: raw draws x, y, z, owner lane (a ring).  It holds what
   // a pass can leave: < 64 points not yet traced, 64 per try of the pass and
   // 16 per owner of the cooperative tail (256 or more entries; a power of 2
@@ -485,10 +511,12 @@ __device__ __forceinline__ int soft_queue(const Geo& p, bool masks, bool need_so
       const d3 Po = mk(__shfl(P.x, ow), __shfl(P.y, ow), __shfl(P.z, ow));
       const d3 Lo = mk(__shfl(ldir.x, ow), __shfl(ldir.y, ow), __shfl(ldir.z, ow));
       const double dist = __shfl(ldist, ow);
-      const Cand co{__shfl(cm.s, ow), p.nt ? __shfl(cm.t, ow) : 0ull};  // (no triangles: cm.t is 0)
+      typename Kind<kSph>::C co;
+      co.s = __shfl(cm.s, ow);
+      if constexpr (!kSph) co.t = p.nt ? __shfl(cm.t, ow) : 0ull;  // (no triangles: cm.t is 0)
       if (lane < n) {
         const d3 pt = mk(rt_bits_to_unit(e.x) * 2 - 1, rt_bits_to_unit(e.y) * 2 - 1, rt_bits_to_unit(e.z) * 2 - 1);
-        if (!shadow_blocked<kCount>(p, masks, Po, normalize(Lo + muls(pt, 0.1)), dist, co, stack, c))
+        if (!shadow_blocked<kCount, kSph>(p, masks, Po, normalize(Lo + muls(pt, 0.1)), dist, co, stack, c))
           atomicAdd(&sq_unocc[ow], 1);
       }
       head += n;
@@ -582,10 +610,14 @@ struct Hot {
   bool recursive, soft, masks;
 };
 extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
-template <bool kStage>
+template <bool kStage, bool kSph = false>
 __device__ __forceinline__ Hot hot(KArg k) {
   Hot h;
   h.g = Geo{k->spheres, k->tris, k->boxes, k->bvh, k->ns, k->nt, k->use_bvh, k->nb};
+  if constexpr (kSph) {  // launch_stream picks these kernels for nt == 0 && nb == 0 only
+    h.g.nt = 0;
+    h.g.nb = 0;
+  }
   h.mats = k->mats;
   h.lights = k->lights;
   h.jump = k->jump;
@@ -609,9 +641,9 @@ __device__ __forceinline__ Hot hot(KArg k) {
   h.masks = !h.g.use_bvh && h.g.ns <= 64 && h.g.nt <= 64;  // shadow-cone culling available
   return h;
 }
-template <bool kStage>
+template <bool kStage, bool kSph = false>
 __device__ __forceinline__ Hot hot() {
-  return hot<kStage>(fresh());
+  return hot<kStage, kSph>(fresh());
 }
 
 // Camera ray of sample s of pixel (x, y): tracePixel's jitter
@@ -1373,6 +1405,13 @@ __device__ __forceinline__ SArg sfresh() {
   return k;
 }
 
+// (kSph) per lane: its path's throughput T, in LDS (render_body path_T; a
+// function's array, so the other instantiations' LDS stays as it is)
+__device__ __forceinline__ double (*tput_lds())[3] {
+  __shared__ double tput[64][3];
+  return tput;
+}
+
 // kStream (render_stream_kernel): no blocks, no visibility
 // phase, no ring and no resolve -- the wave stages the scene once and then
 // takes entries (frame, live pixel, sample) off the launch-wide queue for as
@@ -1382,9 +1421,17 @@ __device__ __forceinline__ SArg sfresh() {
 // one element there.  kBase (render_stream_base_kernel): entry
 // sample s is the frame's sample sample_base + s (a progression's later adds);
 // an instantiation of its own, so the product stream kernel keeps its code.
-template <bool kCount, bool kStage, bool kPilot, bool kSky, bool kTailT, bool kStream = false, bool kBase = false>
+// kSph (render_stream_sph_kernel and its kBase twin): the
+// launch's scene has no triangle and no cube, which is every scene the auto
+// rule streams; the bounce code carries no triangle or cube test, mask, hit
+// field or select (Kind<kSph>).  The other instantiations keep their code.
+template <bool kCount, bool kStage, bool kPilot, bool kSky, bool kTailT, bool kStream = false, bool kBase = false,
+          bool kSph = false>
 __device__ __forceinline__ void render_body(const KParams& pk) {
   static_assert(!kStream || (kStage && !kCount && !kPilot && !kSky && !kTailT), "the stream kernel is the staged product body");
+  static_assert(!kSph || kStream, "spheres-only is a build of the stream kernel");
+  typedef typename Kind<kSph>::C CandK;
+  typedef typename Kind<kSph>::H HitK;
   __shared__ uint32_t hbits[kStream ? 1 : kMaxBlockSamples / 32];  // hit samples of the block
   __shared__ int hoff[kStream ? 2 : kMaxBlockSamples / 32 + 1];    // list offset of each bit word; [words] = #hits
   __shared__ double slot[kStream ? 64 : kRound][3];  // radiance of the round's entries (kStream: of each lane's path)
@@ -1464,7 +1511,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
   int dbg_bprev = -1;
   const unsigned long long tv0 = __builtin_amdgcn_s_memtime();
 #endif
-  const Cand all{~0ull, ~0ull};
+  const CandK all = cand_all<kSph>();
 
   // ---- phase 1: visibility of the block's camera rays
   if constexpr (!kStream) {
@@ -1701,6 +1748,32 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
     slot[q_][1] = v_.y;                  \
     slot[q_][2] = v_.z;                  \
   } while (0)
+    // (kSph: the path's throughput T lives in LDS the same way -- used once
+    // per bounce, after the lighting section, whose registers its six made
+    // one too many at four waves per SIMD)
+#define path_T()                                                       \
+  ({                                                                   \
+    d3 t_;                                                             \
+    if constexpr (kSph) {                                              \
+      double(*tp_)[3] = tput_lds();                                    \
+      t_ = mk(tp_[threadIdx.x][0], tp_[threadIdx.x][1], tp_[threadIdx.x][2]); \
+    } else {                                                           \
+      t_ = T;                                                          \
+    }                                                                  \
+    t_;                                                                \
+  })
+#define set_path_T(v)                    \
+  do {                                   \
+    const d3 v_ = (v);                   \
+    if constexpr (kSph) {                \
+      double(*tp_)[3] = tput_lds();      \
+      tp_[threadIdx.x][0] = v_.x;        \
+      tp_[threadIdx.x][1] = v_.y;        \
+      tp_[threadIdx.x][2] = v_.z;        \
+    } else {                             \
+      T = v_;                            \
+    }                                    \
+  } while (0)
 #define stream_store_row()                                            \
   do {                                                                \
     if constexpr (kStream) {                                          \
@@ -1723,7 +1796,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
       bool shade = false, front = false, fin = false;
       d3 P = mk(0, 0, 0), N = mk(0, 0, 0);
       int mi = 0, self = -1;
-      HitSel hs;
+      HitK hs;
       int outer = 0;  // 1: continue the shade loop, 2: leave it
 #ifdef RT_WG_TIMING
       unsigned long long ts0 = 0;
@@ -1781,8 +1854,15 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
                                   it.x, it.y, (int)fs, rng, o, d, nc);
               skey[lane_now()] = rt_soft_key(fkey, (uint32_t)it.y * (uint32_t)sk->k.W + (uint32_t)it.x, (uint32_t)fs);
               entry = (int)((fl * spp + s) * nlive + i);
-              T = mk(1, 1, 1);
-              set_path_L(mk(0, 0, 0));
+              set_path_T(mk(1, 1, 1));
+              if constexpr (kSph) {
+                // (the zero made here: held in a register pair from the
+                // prologue on, it was spilled at four waves per SIMD)
+                const double z = zero_now();
+                set_path_L(mk(z, z, z));
+              } else {
+                set_path_L(mk(0, 0, 0));
+              }
               depth = 0;
               alive = true;
             }
@@ -2002,7 +2082,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
 
         bool wide_q = false, wide_found = false, wide_fb = false;
         if constexpr (kStage) {  // wave-uniform: few paths left -> helpers
-          const Hot h = hot<kStage>();
+          const Hot h = hot<kStage, kSph>();
           const bool need = alive && !shade && depth < h.max_depth;
           const unsigned long long qm = __ballot(need);
           const int nq = __popcll(qm);
@@ -2010,23 +2090,23 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           // than the short scan they split; measured on the 5-sphere scene)
           if (h.g.nt == 0 && h.g.ns >= 16 && nq > 0 && nq <= 16) {
             // (kCount: helpers count their sphere tests, primary queries included)
-            wide_found = closest_wide<kCount>(h.g, need, qm, nq, o, d, hs, wide_fb, c);
+            wide_found = closest_wide<kCount, kSph>(h.g, need, qm, nq, o, d, hs, wide_fb, c);
             wide_q = true;
           }
         }
         if (alive && !shade) {
-          const Hot h = hot<kStage>();
+          const Hot h = hot<kStage, kSph>();
           const Geo& gg = h.g;
           bool done = depth >= h.max_depth;  // traceRay depth cut-off: contributes 0
           bool missed = false;
           if (!done) {
             if (kCount && depth == 0) {  // phase 1 counted the primary query
               Counters nc;
-              done = (wide_q && !wide_fb) ? !wide_found : !closest_hit<false>(gg, o, d, hs, stack, all, nc);
+              done = (wide_q && !wide_fb) ? !wide_found : !closest_hit<false, kSph>(gg, o, d, hs, stack, all, nc);
             } else {
               cnt<kCount>(c, C_BOUNCE);
               done = (wide_q && !wide_fb) ? !wide_found
-                                          : !closest_hit<kCount>(gg, o, d, hs, stack, all, c);  // miss -> black
+                                          : !closest_hit<kCount, kSph>(gg, o, d, hs, stack, all, c);  // miss -> black
             }
             missed = done;
           }
@@ -2047,7 +2127,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             shade = true;
             cnt<kCount>(c, C_SHADE);
             // HitRecord of the closest primitive (sphere.go:42-58, triangle.go:68-81)
-            if (!hs.is_tri) {
+            if (!hit_is_tri(hs)) {
               const DSphere& S0 = gg.spheres[hs.idx];
               const double t = hs.num / len2(d);
               P = o + muls(d, t);
@@ -2056,7 +2136,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               N = front ? outward : neg(outward);
               mi = S0.mat;
               self = S0.obj;
-            } else {
+            } else if constexpr (!kSph) {
               const DTri& T0 = gg.tris[hs.idx];
               P = o + muls(d, hs.num);
               double w = 1.0 - hs.u - hs.v;
@@ -2084,7 +2164,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
 
       if (__ballot(shade) != 0) {
         // (2) calculateDirectLighting (renderer.go:229-297), light by light
-        const Hot h = hot<kStage>();
+        const Hot h = hot<kStage, kSph>();
         const Geo& gg = h.g;
         const bool masks = h.masks, soft = h.soft;
         const DMat* __restrict__ m = h.mats + mi;
@@ -2094,7 +2174,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           const DLight& Lt = h.lights[li];
           d3 ldir = mk(0, 0, 0);
           double ldist = 0;
-          Cand cm{0ull, 0ull};
+          CandK cm{};
           bool lit = false, occl = false;
 #ifdef RT_WG_TIMING
           const unsigned long long th0 = __builtin_amdgcn_s_memtime();
@@ -2121,23 +2201,26 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               const int ncq = __popcll(cq);
               if (ncq > 0 && ncq <= 16) {
                 const unsigned long long ms = cone_wide(gg, hard, cq, ncq, P, N, front, self, ldir, ldist);
-                if (hard) cm = Cand{ms, 0ull};
+                if (hard) {
+                  cm = CandK{};
+                  cm.s = ms;
+                }
                 wide_c = true;
               }
             }
           }
           if (hard) {
-            if (masks && !wide_c) cm = cone_candidates(gg, P, N, front, self, ldir, ldist);
+            if (masks && !wide_c) cm = cone_candidates<kSph>(gg, P, N, front, self, ldir, ldist);
             if constexpr (kCount) {
               const unsigned long long s0 = c.v[C_SPH], t0 = c.v[C_TRI];
-              occl = shadow_blocked<kCount>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray
+              occl = shadow_blocked<kCount, kSph>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray
               if (dark) {
                 culled.v[C_SHADOW] += 1;
                 culled.v[C_SPH] += c.v[C_SPH] - s0;
                 culled.v[C_TRI] += c.v[C_TRI] - t0;
               }
             } else {
-              occl = shadow_blocked<kCount>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray
+              occl = shadow_blocked<kCount, kSph>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray
             }
           }
 #ifdef RT_WG_TIMING
@@ -2146,7 +2229,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           const bool need_soft = lit && !occl && soft;
           // the 16 soft rays are traced unless their shadow cone is empty or
           // the light is inert (dark: the shading is the same whatever they hit)
-          const bool trace = (!masks || (cm.s | cm.t) != 0) && !dark;
+          const bool trace = (!masks || cand_any(cm)) && !dark;
           int unocc = 0;
           // Spec v4 (include/rt_rng.h): the 16 points come from the stream of
           // (sample, depth, light), not from the path's.  A lane whose rays
@@ -2185,9 +2268,9 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             if (__popcll(owners) <= kCoopMax) {
               for (unsigned long long b = owners; b; b &= b - 1) {
                 const int ow = __builtin_ctzll(b);
-                const CoopOut r = soft_coop<kCount>(
+                const CoopOut r = soft_coop<kCount, kSph>(
                     gg, masks, true, inv3(rl3(P, ow)), inv3(rl3(ldir, ow)),
-                    inv(rld(ldist, ow)), Cand{rl64(cm.s, ow), rl64(cm.t, ow)}, rl64(srng.x, ow), h.jump, stack, c);
+                    inv(rld(ldist, ow)), cand_of_lane(cm, ow), rl64(srng.x, ow), h.jump, stack, c);
                 if (lane == ow) {
                   unocc = r.unocc;
                   cnt<kCount>(c, C_SHADOW, 16);
@@ -2195,7 +2278,8 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
                 }
               }
             } else {
-              const int uq = soft_queue<kCount>(gg, masks, traced_soft, true, P, ldir, ldist, cm, srng, h.jump, stack, c);
+              const int uq =
+                  soft_queue<kCount, kSph>(gg, masks, traced_soft, true, P, ldir, ldist, cm, srng, h.jump, stack, c);
               if (traced_soft) unocc = uq;  // (a free lane keeps its 16)
             }
           }
@@ -2231,13 +2315,13 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           d3 E = ld3(m->emit);
           const Scat sc = scatter<kCount>(m, d, N, front, rng, c);
           if (!sc.ok) {
-            set_path_L(path_L() + mul(T, E + D));
+            set_path_L(path_L() + mul(path_T(), E + D));
             fin = true;
           } else {
-            set_path_L(path_L() + mul(T, E + muls(D, m->dw)));
+            set_path_L(path_L() + mul(path_T(), E + muls(D, m->dw)));
             fin = !h.recursive || depth + 1 >= h.max_depth;
             if (!fin) {
-              T = mul(T, muls(sc.A, m->rw));
+              set_path_T(mul(path_T(), muls(sc.A, m->rw)));
               o = P;
               d = sc.nd;
               depth += 1;
@@ -2268,6 +2352,8 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
   }
 #undef path_L
 #undef set_path_L
+#undef path_T
+#undef set_path_T
 #undef path_q
 #undef stream_store_row
 #ifdef RT_WG_TIMING
@@ -2471,6 +2557,14 @@ __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_stream_kernel(co
 __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_stream_base_kernel(const StreamKArgs a) {
   render_body<false, true, false, false, false, true, true>(a.k);
 }
+// The two for a scene of spheres alone (kSph; launch_stream picks them), with
+// a waves-per-SIMD bound of their own.
+__global__ __launch_bounds__(64, RT_STREAM_SPH_WAVES) void render_stream_sph_kernel(const StreamKArgs a) {
+  render_body<false, true, false, false, false, true, false, true>(a.k);
+}
+__global__ __launch_bounds__(64, RT_STREAM_SPH_WAVES) void render_stream_sph_base_kernel(const StreamKArgs a) {
+  render_body<false, true, false, false, false, true, true, true>(a.k);
+}
 // After it on the same stream: one lane per pixel of the rank's tiles, per
 // frame of the launch (blockIdx.y).  Lane t writes local pixel t black when it
 // is not live (what the block kernel's epilogue writes for it: a sum of +0),
@@ -2518,10 +2612,31 @@ __global__ __launch_bounds__(256) void resolve_rows_kernel(const StreamKArgs a) 
   }
 }
 
-int stream_wave_slots(int device) {
+// The stream kernel of a launch (kStreamKernels of them): bit 0 the kBase
+// twin, bit 1 the spheres-only build.
+typedef void (*StreamKernel)(const StreamKArgs);
+static StreamKernel stream_kernel_fn(int kernel) {
+  switch (kernel) {
+    case 0: return render_stream_kernel;
+    case 1: return render_stream_base_kernel;
+    case 2: return render_stream_sph_kernel;
+    default: return render_stream_sph_base_kernel;
+  }
+}
+int stream_kernel_of(const KParams& p) { return (p.sample_base != 0 ? 1 : 0) | (p.nt == 0 && p.nb == 0 ? 2 : 0); }
+
+// Resident one-wave workgroups of that kernel on `device` (the current one)
+// with `shmem` bytes of dynamic LDS: what the runtime reports per CU for the
+// kernel's own registers and LDS, times the CUs.  0: no answer.
+int stream_wave_slots(int device, int kernel, size_t shmem) {
   hipDeviceProp_t pr;
   if (hipGetDeviceProperties(&pr, device) != hipSuccess || pr.multiProcessorCount <= 0) return 0;
-  return pr.multiProcessorCount * 4 * RT_WAVES_PER_SIMD;  // CUs x SIMDs x waves per SIMD of the kernel
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(stream_kernel_fn(kernel)), 64,
+                                                   shmem) != hipSuccess ||
+      per_cu <= 0)
+    return 0;
+  return pr.multiProcessorCount * per_cu;
 }
 
 int launch_stream(const KParams& pin, const StreamParams& sp, int wgs, void* stream) {
@@ -2540,10 +2655,9 @@ int launch_stream(const KParams& pin, const StreamParams& sp, int wgs, void* str
   if (p.stage_bytes <= 0 || p.use_bvh || wgs <= 0 || sp.frames <= 0 || sp.npix <= 0) return (int)hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(sp.cursor, 0, sizeof(unsigned int), st);
   if (e != hipSuccess) return (int)e;
-  if (p.sample_base != 0)
-    hipLaunchKernelGGL(render_stream_base_kernel, dim3(wgs), dim3(64), render_shmem(p), st, a);
-  else
-    hipLaunchKernelGGL(render_stream_kernel, dim3(wgs), dim3(64), render_shmem(p), st, a);
+  // (a scene without triangles and cubes -- every scene the auto rule streams
+  // -- takes the spheres-only build; triangles streamed by force the generic one)
+  hipLaunchKernelGGL(stream_kernel_fn(stream_kernel_of(p)), dim3(wgs), dim3(64), render_shmem(p), st, a);
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(resolve_rows_kernel, dim3((unsigned)((sp.npix + 255) / 256), (unsigned)sp.frames), dim3(256), 0, st, a);

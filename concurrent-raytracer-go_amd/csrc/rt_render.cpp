@@ -406,9 +406,17 @@ static int render_stream(rt_context* c, const KParams& p, const rt_settings* st,
   if (per_entries > 0) fit = std::min(budget / per_bytes, (size_t)0x7FFFFFFF / per_entries);
   const int group = (int)std::min<size_t>((size_t)nframes, fit);
   if (group < std::min(nframes, 2)) return RT_OK;
-  if (c->wave_slots <= 0) c->wave_slots = stream_wave_slots(c->device);
-  if (c->wave_slots <= 0) {
-    set_error("stream launch: the device reports no compute units");
+  // the grid: the resident waves of the kernel this launch takes (cached per
+  // kernel; a new scene can change its dynamic LDS)
+  const int kid = stream_kernel_of(p);
+  const size_t shmem = render_shmem(p);
+  if (c->wave_slots[kid] <= 0 || c->wave_shmem[kid] != shmem) {
+    c->wave_slots[kid] = stream_wave_slots(c->device, kid, shmem);
+    c->wave_shmem[kid] = shmem;
+  }
+  const int wave_slots = c->wave_slots[kid];
+  if (wave_slots <= 0) {
+    set_error("stream launch: the device reports no resident waves for the stream kernel");
     return RT_E_DEVICE;
   }
   // [cursor word, 256 B][rows of the largest group]
@@ -430,7 +438,7 @@ static int render_stream(rt_context* c, const KParams& p, const rt_settings* st,
     sp.frame0 = f0;
     sp.frames = std::min(group, nframes - f0);
     sp.total = (uint32_t)((size_t)sp.frames * per_entries);
-    const int e = launch_stream(p, sp, c->wave_slots, s);
+    const int e = launch_stream(p, sp, wave_slots, s);
     if (e != hipSuccess) return launch_failed("stream", e);
     c->stats.stream_launches += 1;
   }

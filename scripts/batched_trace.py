@@ -54,6 +54,13 @@ def main():
     names = [r["Kernel_Name"] for r in rows]
     counting = next(i for i, n in enumerate(names) if "render_kernel<true" in n)
     dom = [r for r in rows[counting + 1:] if kname in r["Kernel_Name"]]
+    if len(dom) < n_warm + len(frames):
+        # the launches streamed: their kernel is the stream
+        # kernel, spheres-only or generic, not the line's block kernel
+        dom = [r for r in rows[counting + 1:] if "render_stream_sph_kernel" in r["Kernel_Name"] or
+               "render_stream_kernel" in r["Kernel_Name"]]
+        if dom:
+            kname = dom[0]["Kernel_Name"]
     timed = dom[n_warm:n_warm + len(frames)]
     launches = []
     for r, f in zip(timed, frames):

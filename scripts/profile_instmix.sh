@@ -36,9 +36,11 @@ for scene in ${INSTMIX_SCENES:-headline c4}; do
   else
     suf=$([ $FR = 1 ] && echo "" || echo "_b$FR")
     # a batched launch of the headline streams by default: its
-    # kernel is the one to report, as *_headline_bB_stream.json
+    # kernel is the one to report, as *_headline_bB_stream.json -- the
+    # spheres-only build (INSTMIX_STREAM_KERNEL=render_stream_kernel: a library
+    # from before it)
     if [ $FR != 1 ]; then
-      python3 scripts/pmc_instmix.py "render_stream_kernel" \
+      python3 scripts/pmc_instmix.py "${INSTMIX_STREAM_KERNEL:-render_stream_sph_kernel}" \
         "$(dirname "${dirs[0]}")/profiles_${R}/${R}_instmix_headline${suf}_stream.json" "${dirs[@]}"
       continue
     fi
