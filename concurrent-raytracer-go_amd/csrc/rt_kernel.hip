@@ -36,6 +36,20 @@
 // only feed range tests are filtered by a reciprocal multiply with a 2^-40
 // relative margin; the exact IEEE division runs whenever the filter cannot
 // decide.
+//
+// Map of the render kernels' one body (render_body<V>, V a variant type that
+// names its switches: BlockBody<..>, TailBody, Stream..Body):
+//   phase 1 (visibility) and the hit-list scan    inline in render_body
+//   the hit list, entry -> sample id              HitList::entry_id
+//   phase 2, a pass's refill                      ring_low, resolve_entries, block_entry;
+//                                                 the stream kernel: stream_claim_chunk, stream_entry
+//   the tail export of pass 0                     tail_reserve, tail_pixel_row, the rest inline (next to
+//                                                 them: tail_helper)
+//   closest hit, lighting, soft shadows, scatter  closest_hit / closest_wide, cone_candidates / cone_wide,
+//                                                 shadow_blocked, soft_coop, soft_queue, scatter (rt_device.h)
+//   the pilot's path lengths                      pilot_record
+//   phase 3 (final)                               inline, tail_rows_give_back, reduce_counters
+//   RT_WG_TIMING clocks and records               WgClock
 #include <hip/hip_runtime.h>
 
 #include "../../include/rt_rng.h"
@@ -659,6 +673,172 @@ __device__ __forceinline__ void camera_ray(KArg k, int x, int y, int s, rt_rng& 
   camera_ray_c<kCount>(cam_k(k), k->cf, x, y, s, rng, o, d, c);
 }
 
+// ------------------------------------------------------------ workgroup clocks
+// RT_WG_TIMING builds (make timing; scripts/wg_timing.py and
+// scripts/latency_probe.py read the records): every counter and stamp of a
+// workgroup, and the writers of its kDbgStride words of KParams.dbg.  In every
+// other build the struct is empty and so is each method, so render_body,
+// solo_path and tail_helper call them unconditionally.
+//   a block's (or a stream wave's) record: r[0] start, r[1] loop end, r[2] end
+//     (s_memrealtime); r[3..12] wave-uniform section clocks (s_memtime) and
+//     counts: hit, lighting, soft, phase 1 (visibility), shade iterations,
+//     cone + hard shadow, scatter, lane-iterations alive, coop owners served,
+//     soft_queue passes; r[13] np * 65536 + ns, r[14] split slot + 1 (a stream
+//     wave: 0, 0); r[16 + i] the stamp of shade iteration 4 i (i < 16), or --
+//     when a lone path ran -- its section clocks; r[32..36] / r[37..41]
+//     shade-iteration clocks / counts by live lanes (1, 2, 3-4, 5-8, > 8);
+//     r[42] lone-path bounces, r[43] entries into solo_path;
+//   a tail helper's record: r[0] start, r[1] first path, r[2] end, r[3] ticks in
+//     solo_path, r[4..6] the last path's start and its depth when exported and
+//     at its end, r[7] paths, r[8] their bounces, r[14] = -1;
+//   a lone path's bounce by section (solo_clk[k], wave-uniform; PROBE_SECTIONS
+//     of scripts/latency_probe.py): 0 loop top + closest hit, 1 hit record,
+//     2 stream tries + light vectors + cones + hard rays, 3 soft rays,
+//     4 lighting terms, 5 scatter, 6 bounces, 7 entries; solo_mark(k), k >= 8:
+//     clocks from the start of the current section to that point of it (the
+//     parallel-lights form: 8 tries, 9 light vectors, 10 their shuffles,
+//     11 cones + hard rays + ballots; 12 the soft rays of tries 0..63, 13 of
+//     tries 64..127; 14 the lighting terms before the sum).
+enum WgSection { kClkHit, kClkLight, kClkSoft, kClkHard, kClkScat };
+#ifdef RT_WG_TIMING
+__shared__ unsigned long long solo_clk[16];
+struct WgClock {
+  unsigned long long t_start = 0, t_loop = 0, iter = 0;
+  unsigned long long sec[5] = {0, 0, 0, 0, 0}, from[5] = {0, 0, 0, 0, 0};  // by WgSection: clocks, start of the open one
+  unsigned long long vis = 0, alive = 0, coop = 0, seq = 0;
+  // by live lanes (vectors: indexed by a variable, and an array member so
+  // indexed would keep the whole struct in scratch)
+  typedef unsigned long long Buckets __attribute__((ext_vector_type(5)));
+  Buckets bclk = {0, 0, 0, 0, 0}, bcnt = {0, 0, 0, 0, 0};
+  unsigned long long bts = 0;
+  int bprev = -1;
+  unsigned long long solo_t0 = 0;  // solo_path: start of the current section
+  // tail_helper: first and last path's start, the last one's depths, paths, their ticks and bounces
+  unsigned long long first = 0, last = 0, last_d0 = 0, last_d1 = 0, paths = 0, solo = 0, bounces = 0;
+
+  __device__ __forceinline__ unsigned long long* record(KArg k) const { return k->dbg + (size_t)blockIdx.x * kDbgStride; }
+  __device__ __forceinline__ void start(int lane) {
+    if (lane < 16) solo_clk[lane] = 0;
+    t_start = __builtin_amdgcn_s_memrealtime();
+    vis = __builtin_amdgcn_s_memtime();
+  }
+  __device__ __forceinline__ void visibility_done() { vis = __builtin_amdgcn_s_memtime() - vis; }
+  // a shade iteration starts with `alive` lanes running paths (pass 0); opens kClkHit
+  __device__ __forceinline__ void iteration(bool is_alive, int lane) {
+    ++iter;
+    alive += __popcll(__ballot(is_alive));
+    {
+      const unsigned long long now = __builtin_amdgcn_s_memtime();
+      if (bprev >= 0) bclk[bprev] += now - bts;
+      const int nal = __popcll(__ballot(is_alive));
+      bprev = nal == 1 ? 0 : (nal == 2 ? 1 : (nal <= 4 ? 2 : (nal <= 8 ? 3 : 4)));
+      bcnt[bprev] += 1;
+      bts = now;
+    }
+    if (iter % 4 == 0 && iter / 4 < 16 && lane == 0 && fresh()->dbg) record(fresh())[16 + iter / 4] = __builtin_amdgcn_s_memrealtime();
+    from[kClkHit] = __builtin_amdgcn_s_memtime();
+  }
+  __device__ __forceinline__ void begin(WgSection s) { from[s] = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void end(WgSection s) { sec[s] += __builtin_amdgcn_s_memtime() - from[s]; }
+  // kClkHit ends where kClkLight begins: one clock read
+  __device__ __forceinline__ void hit_done() {
+    from[kClkLight] = __builtin_amdgcn_s_memtime();
+    sec[kClkHit] += from[kClkLight] - from[kClkHit];
+  }
+  __device__ __forceinline__ void soft_form(unsigned long long owners) {
+    if (__popcll(owners) <= kCoopMax) coop += __popcll(owners); else ++seq;
+  }
+  __device__ __forceinline__ void loop_done() {
+    t_loop = __builtin_amdgcn_s_memrealtime();
+    if (bprev >= 0) bclk[bprev] += __builtin_amdgcn_s_memtime() - bts;
+  }
+  // the record of a block (shape = np * 65536 + ns, split = slot + 1) or of a
+  // stream wave (block = false: zeros there and for the lone-path words)
+  __device__ __forceinline__ void write(KArg k, int lane, bool block, unsigned long long shape, unsigned long long split) const {
+    if (k->dbg && lane == 0) {
+      unsigned long long* r = record(k);
+      r[0] = t_start;
+      r[1] = t_loop;
+      r[2] = __builtin_amdgcn_s_memrealtime();
+      r[3] = sec[kClkHit];
+      r[4] = sec[kClkLight];
+      r[5] = sec[kClkSoft];
+      r[6] = vis;
+      r[7] = iter;
+      r[8] = sec[kClkHard];
+      r[9] = sec[kClkScat];
+      r[10] = alive;
+      r[11] = coop;
+      r[12] = seq;
+      r[13] = shape;
+      r[14] = split;
+      for (int i = 0; i < 5; ++i) {
+        r[32 + i] = bclk[i];
+        r[37 + i] = bcnt[i];
+      }
+      if (block && solo_clk[6])  // a lone path ran: its section clocks replace the iteration stamps
+        for (int i = 0; i < 16; ++i) r[16 + i] = solo_clk[i];
+      r[42] = block ? solo_clk[6] : 0;  // lone-path bounces (0: none ran)
+      r[43] = block ? solo_clk[7] : 0;  // entries into solo_path
+    }
+  }
+  __device__ __forceinline__ void stream_write(int lane) const { write(fresh(), lane, false, 0, 0); }
+  // solo_path
+  __device__ __forceinline__ void solo_start() { solo_t0 = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void solo_count(int k) { solo_clk[k] += 1; }
+  __device__ __forceinline__ void solo_lap(int k) {  // section k ends here, the next one starts
+    const unsigned long long now = __builtin_amdgcn_s_memtime();
+    solo_clk[k] += now - solo_t0;
+    solo_t0 = now;
+  }
+  __device__ __forceinline__ void solo_mark(int k) { solo_clk[k] += __builtin_amdgcn_s_memtime() - solo_t0; }
+  // tail_helper: a path taken at t_path ran from depth d0 to d1; the helper's record at its end
+  __device__ __forceinline__ void helper_path(unsigned long long t_path, int d0, int d1) {
+    if (!first) first = t_path;
+    paths += 1;
+    solo += __builtin_amdgcn_s_memrealtime() - t_path;
+    last = t_path;
+    last_d0 = (unsigned long long)d0;
+    last_d1 = (unsigned long long)d1;
+    bounces += (unsigned long long)(d1 - d0);
+  }
+  __device__ __forceinline__ void helper_write(KArg k, int lane, unsigned long long t_born) const {
+    if (k->dbg && lane == 0) {
+      unsigned long long* r = record(k);
+      r[0] = t_born;
+      r[1] = first;
+      r[2] = __builtin_amdgcn_s_memrealtime();
+      r[3] = solo;
+      r[4] = last;     // the last path's start,
+      r[5] = last_d0;  // its depth when exported,
+      r[6] = last_d1;  // and at its end
+      r[7] = paths;
+      r[8] = bounces;
+      r[14] = ~0ull;
+    }
+  }
+};
+#else
+struct WgClock {
+  __device__ __forceinline__ void start(int) {}
+  __device__ __forceinline__ void visibility_done() {}
+  __device__ __forceinline__ void iteration(bool, int) {}
+  __device__ __forceinline__ void begin(WgSection) {}
+  __device__ __forceinline__ void end(WgSection) {}
+  __device__ __forceinline__ void hit_done() {}
+  __device__ __forceinline__ void soft_form(unsigned long long) {}
+  __device__ __forceinline__ void loop_done() {}
+  __device__ __forceinline__ void write(KArg, int, bool, unsigned long long, unsigned long long) const {}
+  __device__ __forceinline__ void stream_write(int) const {}
+  __device__ __forceinline__ void solo_start() {}
+  __device__ __forceinline__ void solo_count(int) {}
+  __device__ __forceinline__ void solo_lap(int) {}
+  __device__ __forceinline__ void solo_mark(int) {}
+  __device__ __forceinline__ void helper_path(unsigned long long, int, int) {}
+  __device__ __forceinline__ void helper_write(KArg, int, unsigned long long) const {}
+};
+#endif
+
 // ------------------------------------------------------------ solo paths
 // When a single path is left running in a wave (the end of a block, where
 // a long metal-metal interreflection sets the launch's critical path), the
@@ -772,36 +952,6 @@ __device__ __forceinline__ void solo_take16(const SoloTries& t, int& ia, int& ib
   ib = b16 ? __builtin_ctzll(b16) + 1 : -1;
 }
 
-// RT_WG_TIMING builds: s_memtime clocks of a lone path's bounce by section
-// (solo_clk[k], wave-uniform; scripts/latency_probe.py PROBE_SECTIONS):
-// 0 loop top + closest hit, 1 hit record, 2 stream tries + light vectors +
-// cones + hard rays, 3 soft rays, 4 lighting terms, 5 scatter, 6 bounces,
-// 7 entries;
-// SOLO_S(k), k >= 8: clocks from the start of the current section to that
-// point of it (the parallel-lights form: 8 tries, 9 light vectors, 10 their
-// shuffles, 11 cones + hard rays + ballots; 12 the soft rays of tries
-// 0..63, 13 of tries 64..127; 14 the lighting terms before the sum)
-#ifdef RT_WG_TIMING
-__shared__ unsigned long long solo_clk[16];
-#define SOLO_T(k)                                          \
-  do {                                                     \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-    solo_clk[k] += now_ - solo_t0;                         \
-    solo_t0 = now_;                                        \
-  } while (0)
-#define SOLO_S(k)                                                           \
-  do {                                                                      \
-    solo_clk[k] += __builtin_amdgcn_s_memtime() - solo_t0;                  \
-  } while (0)
-#else
-#define SOLO_T(k) \
-  do {            \
-  } while (0)
-#define SOLO_S(k) \
-  do {            \
-  } while (0)
-#endif
-
 // The path of lane `ow`, run to its end by the whole wave: its radiance.
 // A real call (RT_SOLO_CALL, the default): its registers then do not add to
 // the shade loop's, whose per-iteration scratch spills they caused when it
@@ -837,9 +987,8 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
   rt_rng rng{rl64(rx, ow)};
   depth = (int)rl32((uint32_t)depth, ow);
   Counters c;
-#ifdef RT_WG_TIMING
-  unsigned long long solo_t0 = __builtin_amdgcn_s_memtime();
-#endif
+  WgClock clk;  // (the lone path's section clocks, RT_WG_TIMING builds)
+  clk.solo_start();
   // the parallel lighting form (solo_lights): sphere-only scenes with one or
   // two lights, a (light, sphere) pair per lane
   bool par;
@@ -852,9 +1001,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
     jA = h0.jump[2 * lane];
     jC = h0.jump[2 * lane + 1];
   }
-#ifdef RT_WG_TIMING
-  solo_clk[7] += 1;
-#endif
+  clk.solo_count(7);
   for (;;) {
     const Hot h = hot<true>(launder(karg));
     const Geo& g = h.g;
@@ -862,13 +1009,11 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
       if (dep_out) *dep_out = depth;
       return L;
     }
-#ifdef RT_WG_TIMING
-    solo_clk[6] += 1;
-#endif
+    clk.solo_count(6);
     // (1) closest hit (hitWorld, renderer.go:170)
     HitSel hs;
     const bool found = solo_closest(g, o, d, hs);
-    SOLO_T(0);
+    clk.solo_lap(0);
     if (!found) {  // miss -> black (or the opted-in sky)
       if constexpr (kSky) L = L + mul(T, sky_color(launder(karg)->sky, d));
       if (dep_out) *dep_out = depth + 1;
@@ -897,7 +1042,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
       mi = T0.mat;
       self = T0.obj;
     }
-    SOLO_T(1);
+    clk.solo_lap(1);
     // (2) calculateDirectLighting (renderer.go:229-297)
     const DMat* __restrict__ m = h.mats + mi;
     d3 D = mk(m->ambient, m->ambient, m->ambient);
@@ -910,7 +1055,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
       const int nl = h.nl, ns = g.ns;
       SoloTries tr{};
       if (h.soft) tr = solo_tries(rt_soft_state(skey, (uint32_t)depth, 0u), rt_soft_state(skey, (uint32_t)depth, 1u), jA, jC);
-      SOLO_S(8);
+      clk.solo_mark(8);
       d3 lvd = mk(0, 0, 0);
       double lvl = 0;
       // the lighting terms' parts that do not depend on the shadows (lane
@@ -939,11 +1084,11 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
       // (light values move across lanes by shuffles where they are used: held
       // as wave-uniform values they would take SGPRs the bounce loop needs)
       const unsigned long long litm = __ballot(lane < nl && !(lvl < 0.001));
-      SOLO_S(9);
+      clk.solo_mark(9);
       const int lj = lane >= ns ? 1 : 0, sj = lane - lj * ns;  // this lane's pair
       const d3 ldj = mk(__shfl(lvd.x, lj), __shfl(lvd.y, lj), __shfl(lvd.z, lj));
       const double dlj = __shfl(lvl, lj);
-      SOLO_S(10);
+      clk.solo_mark(10);
       bool cone = false, blk = false;
       if (lane < nl * ns && ((litm >> lj) & 1ull)) {
         const DSphere& S = g.spheres[sj];
@@ -957,7 +1102,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
         blk = sphere_query(S, P, ldj, a, approx_rcp(a), 0.001, dlj, num) != 0;
       }
       const unsigned long long cones = __ballot(cone), blks = __ballot(blk);
-      SOLO_S(11);
+      clk.solo_mark(11);
       const unsigned long long sm = ns >= 64 ? ~0ull : (1ull << ns) - 1ull;
       const unsigned long long cm0 = cones & sm, cm1 = (cones >> ns) & sm;
       const bool lit0 = litm & 1ull, lit1 = (litm >> 1) & 1ull;
@@ -968,7 +1113,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
       int i16a = -1, i16b = -1;
       solo_take16(tr, i16a, i16b);
       const int e0 = need0 ? i16a : 0, e1 = need1 ? i16b : 0;
-      SOLO_T(2);
+      clk.solo_lap(2);
       int un0 = 16, un1 = 16;
       if (e0 >= 0 && e1 >= 0) {
         int cnt0 = 0, cnt1 = 0;
@@ -993,9 +1138,9 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
             }
           }
           (half ? cnt1 : cnt0) = __popcll(__ballot(acc && in && !occ));
-          if (half == 0) SOLO_S(12);
+          if (half == 0) clk.solo_mark(12);
         }
-        SOLO_S(13);
+        clk.solo_mark(13);
         un0 = cnt0;
         un1 = cnt1;
       } else {
@@ -1009,7 +1154,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
           (li ? un1 : un0) = r.unocc;
         }
       }
-      SOLO_T(3);
+      clk.solo_lap(3);
       // the lighting terms of light lane (< nl), then D in light order
       d3 tdif = mk(0, 0, 0), tspec = mk(0, 0, 0);
       if (lane < nl) {
@@ -1019,7 +1164,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
         tdif = muls(ld3(m->albedo), di * sf);
         if (metallic > 0.5) tspec = muls(ld3(h.lights[lane].color), sii * sf * metallic * 3.0);
       }
-      SOLO_S(14);
+      clk.solo_mark(14);
 #pragma unroll
       for (int li = 0; li < 2; ++li) {
         if (li >= nl) break;
@@ -1031,7 +1176,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
           if (metallic > 0.5) D = D + rl3(tspec, li);
         }
       }
-      SOLO_T(4);
+      clk.solo_lap(4);
     } else
     for (int li = 0; li < h.nl; ++li) {
       const DLight& Lt = h.lights[li];
@@ -1097,7 +1242,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
     // (3) Material.Scatter and the traceRay combination (renderer.go:181-226)
     const d3 E = ld3(m->emit);
     const Scat sc = scatter<false>(m, d, N, front, rng, c);
-    SOLO_T(5);
+    clk.solo_lap(5);
     if (!sc.ok) {
       if (dep_out) *dep_out = depth + 1;
       return L + mul(T, E + D);
@@ -1145,6 +1290,46 @@ constexpr int kRound = 128;  // list entries shaded per round (LDS radiance slot
 #define RT_REFILL2_MIN 16
 #endif
 constexpr int kRefill2Min = RT_REFILL2_MIN;
+
+// The block's hit list: its hit samples' ids, ascending, as a view over
+// render_body's hit bits (`bits`, one per sample id, set by phase 1) and the
+// list offset of each bit word (`off`; off[nwords] = the number of hits).
+template <int kWords>
+struct HitList {
+  uint32_t (&bits)[kWords];
+  int (&off)[kWords + 1];
+  const int& nwords;
+  // sample id (pixel * ns + sample - s0) of hit-list entry e < off[nwords]: the bit
+  // word holding it (the last word whose list offset is <= e, by binary
+  // search over off), then the (e - offset)-th set bit of that word.  No
+  // materialized list: its 2 KB of LDS cost occupancy.
+  __device__ __forceinline__ int entry_id(int e) const {
+    int w = 0;
+    for (int step = 16; step; step >>= 1)
+      if (w + step < nwords && off[w + step] <= e) w += step;
+    uint32_t word = bits[w];
+    int k = e - off[w], pos = 0;
+    for (int sh = 16; sh; sh >>= 1) {
+      const int n = __popc(word & ((1u << sh) - 1u));
+      if (k >= n) {
+        k -= n;
+        word >>= sh;
+        pos += sh;
+      }
+    }
+    return w * 32 + pos;
+  }
+};
+// (kPilot, a measuring render) a path of `depth + 1` bounces ended: its
+// pixel's longest path and its bounces
+template <int kWords>
+__device__ __forceinline__ void pilot_record(const HitList<kWords>& hl, int entry, int depth) {
+  KArg k = fresh();
+  const BlockLoc loc = block_loc(k, block_of(k));
+  const size_t px = (size_t)loc.lt * 1024 + loc.p0 + hl.entry_id(entry) / loc.ns;
+  atomicMax(k->work_max + px, (unsigned)depth + 1u);
+  atomicAdd(k->work_sum + px, (unsigned)depth + 1u);
+}
 
 // ---- tail helpers (TailCtl in rt_internal.h)
 // Device-scope hand-offs on MI355X (MI355X_MICROARCH.md, inter-workgroup
@@ -1237,10 +1422,7 @@ __device__ __forceinline__ void tail_helper(KArg karg, int* stack, double (*buf)
   const unsigned long long t_born = __builtin_amdgcn_s_memrealtime();
   unsigned long long t_idle = t_born;
   int polls = 0;
-#ifdef RT_WG_TIMING
-  unsigned long long dbg_first = 0, dbg_paths = 0, dbg_solo = 0, dbg_last = 0, dbg_last_d0 = 0, dbg_last_d1 = 0,
-                     dbg_bounces = 0;
-#endif
+  WgClock clk;
   for (;;) {
     int idx = -1;
     if (lane == 0) {
@@ -1302,15 +1484,7 @@ __device__ __forceinline__ void tail_helper(KArg karg, int* stack, double (*buf)
     int dep_end = depth;
     const d3 L = solo_path<false>(karg, 0, o, d, T, L0, rx, depth, sk, stack, &dep_end);
     const KArg k = launder(karg);
-#ifdef RT_WG_TIMING
-    if (!dbg_first) dbg_first = t_path;
-    dbg_paths += 1;
-    dbg_solo += __builtin_amdgcn_s_memrealtime() - t_path;
-    dbg_last = t_path;
-    dbg_last_d0 = (unsigned long long)depth;
-    dbg_last_d1 = (unsigned long long)dep_end;
-    dbg_bounces += (unsigned long long)(dep_end - depth);
-#endif
+    clk.helper_path(t_path, depth, dep_end);
     const int spp = k->spp_total, bw = (spp + 31) >> 5;
     int last = 0;
     if (lane == 0) {
@@ -1363,21 +1537,7 @@ __device__ __forceinline__ void tail_helper(KArg karg, int* stack, double (*buf)
     t_idle = __builtin_amdgcn_s_memrealtime();
   }
   int gone = 0;
-#ifdef RT_WG_TIMING
-  if (k0->dbg && lane == 0) {  // a helper's record: start, first path, end, paths, their ticks; [14] = -1
-    unsigned long long* r = k0->dbg + (size_t)blockIdx.x * kDbgStride;
-    r[0] = t_born;
-    r[1] = dbg_first;
-    r[2] = __builtin_amdgcn_s_memrealtime();
-    r[3] = dbg_solo;
-    r[4] = dbg_last;     // the last path's start,
-    r[5] = dbg_last_d0;  // its depth when exported,
-    r[6] = dbg_last_d1;  // and at its end
-    r[7] = dbg_paths;
-    r[8] = dbg_bounces;
-    r[14] = ~0ull;
-  }
-#endif
+  clk.helper_write(k0, lane, t_born);
   if (lane == 0) {
     atomicAdd(&ctl->helper_ticks, (unsigned int)(__builtin_amdgcn_s_memrealtime() - t_born));
     atomicAdd(ctl->gate, ~0ull << 32);  // one helper fewer (-2^32)
@@ -1392,6 +1552,82 @@ __device__ __forceinline__ void tail_helper(KArg karg, int* stack, double (*buf)
       ctl->gate[0] = 0;
       ctl->rows_used[0] = 0;
       ctl->helpers_gone[0] = 0;
+    }
+  }
+}
+
+// A block's export of a path, in parts (render_body, pass 0 of a shade
+// iteration).  tail_reserve: a helper for it (paths in flight < live helpers:
+// the gate word is read first, so draining waves do not add to it in vain)
+// and a queue entry; -1: no helper is free.
+__device__ __forceinline__ int tail_reserve(KArg k) {
+  const int lane = threadIdx.x;
+  TailCtl* ctl = k->tail;
+  int idx = -1;
+  if (lane == 0) {
+    const unsigned long long g0 = __hip_atomic_load(ctl->gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((uint32_t)g0 < (uint32_t)(g0 >> 32)) {
+      const unsigned long long g = atomicAdd(ctl->gate, 1ull);
+      if ((uint32_t)g < (uint32_t)(g >> 32)) {
+        const unsigned int t = atomicAdd(ctl->tail, 1u);
+        if (t < (unsigned int)k->tail_cap) idx = (int)t;  // (entries past the cap are never taken)
+      }
+      if (idx < 0) atomicAdd(ctl->gate, ~0ull);
+    }
+  }
+  return __builtin_amdgcn_readfirstlane(idx);
+}
+// ... and the dynamic row of block pixel p, whose sample sl is exported: a
+// new one (one row per export at most: rows_used < cap), or the one it has
+__device__ __forceinline__ int tail_pixel_row(KArg k, int p, int sl, int64_t oi, int (&prow)[64], short (&pk0)[64]) {
+  const int lane = threadIdx.x;
+  TailCtl* ctl = k->tail;
+  int r = prow[p];
+  if (r < 0) {
+    if (lane == 0) r = (int)atomicAdd(ctl->rows_used, 1u);
+    r = __builtin_amdgcn_readfirstlane(r);
+    const int bw = (k->spp_total + 31) >> 5;
+    for (int w = lane; w < bw; w += 64) st_wt32(k->tail_bits + (size_t)r * bw + w, 0u);
+    if (lane == 0) {
+      TailRow* hd = k->tail_hdr + r;
+      st_wt32(&hd->counter, 2u);  // the block's own share (given back in its epilogue) + this path
+      st_wt32(&hd->k0, (uint32_t)sl);
+      st_wt32(&hd->frame, (uint32_t)frame_of(k));
+      st_wt64(&hd->oi, (uint64_t)oi);
+      prow[p] = r;
+      pk0[p] = (short)sl;
+    }
+  } else if (lane == 0) {
+    pk0[p] = (short)min((int)pk0[p], sl);
+    atomicAdd(&k->tail_hdr[r].counter, 1);  // one more path owes the row a sample
+  }
+  return r;
+}
+// The epilogue of a block with exported paths (render_body, phase 3): the
+// block gives back its share of each of its pixels' rows (the running sum of
+// the samples before the row's first one), and the row's last contributor
+// sums it and writes the pixel
+__device__ __forceinline__ void tail_rows_give_back(KArg k, const BlockLoc& blk, int lane3, double (*slot)[3],
+                                                    double (*psum)[3], const int* prow, const short* pk0) {
+  if (k->tail != nullptr && blk.slot < 0) {
+    int last = 0;
+    if (prow[lane3] >= 0) {
+      TailRow* hd = k->tail_hdr + prow[lane3];
+      st_wtd(hd->prefix, psum[lane3][0]);
+      st_wtd(hd->prefix + 1, psum[lane3][1]);
+      st_wtd(hd->prefix + 2, psum[lane3][2]);
+      st_wt32(&hd->k0, (uint32_t)pk0[lane3]);
+    }
+    wt_drain();  // (the resolve's row samples too) before the counter
+    if (prow[lane3] >= 0) last = atomicSub(&k->tail_hdr[prow[lane3]].counter, 1) == 1 ? 1 : 0;
+    for (unsigned long long b = __ballot(last); b; b &= b - 1) {
+      const int r = prow[__builtin_ctzll(b)], spp = k->spp_total, bw = (spp + 31) >> 5;
+      const TailRow* hd = k->tail_hdr + r;
+      double a = lane3 < 3 ? ld_wtd(hd->prefix + lane3) : 0.0;
+      a = row_sum<true>(slot, k->tail_rows + (size_t)r * spp * 3, k->tail_bits + (size_t)r * bw, (int)ld_wt32(&hd->k0),
+                        spp, a, lane3);
+      const double sx = rld(a, 0), sy = rld(a, 1), sz = rld(a, 2);
+      if (lane3 == 0) store_pixel(k, (int)ld_wt32(&hd->frame), (size_t)ld_wt64(&hd->oi), sx, sy, sz);
     }
   }
 }
@@ -1412,6 +1648,211 @@ __device__ __forceinline__ double (*tput_lds())[3] {
   return tput;
 }
 
+// ------------------------------------------------------------ render_body's phases
+// (each inlined into render_body, which declares the LDS arrays they work on
+// and keeps the path state; DESIGN.md §4.1 maps the phases to these names)
+//
+// Every function here (and HitList, pilot_record, tail_reserve,
+// tail_pixel_row and tail_rows_give_back above) was cut out of render_body under one rule: the
+// 22 kernels of this file keep their instructions and registers, bit for bit
+// (make isa + scripts/cmp_kernels.py against the commit before, the product
+// build and the cross-lane checking build).  What that rule allowed, for the
+// next cut:
+//   - a path-state variable of render_body whose address was never taken
+//     (alive, entry, depth, T, next, resolved, qbeg, qend, dry, blk) goes in
+//     BY VALUE and comes back as the RETURN value; handed over by reference
+//     it is no longer promoted to registers before the inlining, and the
+//     kernels came out with other registers and spill slots.  rng, o, d, c
+//     and the hit selection already went to helpers by reference and may;
+//   - a `for` loop that stands before the pass loop cannot leave
+//     render_body: render_kernel_tail carries the compiler's number of the
+//     pass loop's exit as an immediate (s_mov_b32 s10, 16), and every loop
+//     moved out before it renumbers it.
+// Seams tried and left inline for that reason, each alone against the parent
+// (kernels that differed; lines of their disassembly):
+//   LDS staging of the scene prefix   render_kernel<0,1,0,0>, <0,1,1,0>: 14 of 10875 / 11281
+//                                     (SGPR spill lanes renumbered); render_kernel_tail: 4 (the immediate)
+//   phase 1, visibility               7 block kernels: 4 .. 187 lines (spill lanes, scratch stores
+//                                     reordered); render_kernel_tail: 4 (the immediate)
+//   the hit-list scan                 render_kernel<1,0,0,0>: 170 of 15954 (scratch stores reordered);
+//                                     render_kernel_tail: 9 (the immediate, two VGPRs swapped)
+//   the stream claim as one function  the 4 stream kernels: 5164 .. 6841 lines (registers)
+//   the ring's refill as one function render_kernel_tail and the 4 stream kernels: all lines; 11
+//                                     kernels with other VGPR / spill counts
+//   the tail export as one function,  render_kernel_tail: 16596 .. 18754 of 20406 lines (registers;
+//   per path, or its record's store   same VGPRs, SGPRs and scratch)
+//   the hit record from HitK          13 kernels, 9312 .. 18680 lines; 10 with other register counts
+//                                     (by reference, by value and as a returned struct alike)
+//   the split pixel's last-finisher   9 block kernels: 1 line (s_and_b64's operands swapped), or all
+//   sum, the pixel write              lines; 8 block kernels: 2 lines (two ds_reads swapped)
+// The per-light lighting body and scatter-and-combine rest on that state
+// (D, P, N, shade, fin, o, d, depth, T, L) throughout and were not cut.
+
+// ---- phase 3, as the ring moves on: entries [a, b) of the hit list (all
+// finished, their radiance in their ring slots) are added to their pixels'
+// sums in order; a split pixel's block stores them in its radiance slot row
+// instead (and a pixel with exported paths, kTail, in its tail row)
+template <bool kTail, int kWords, int kSlots, int kPix, int kRows, int kMarks>
+__device__ __forceinline__ void resolve_entries(const HitList<kWords>& hl, const int& nh, const BlockLoc& blk,
+                                                double (&slot)[kSlots][3], double (&psum)[kPix][3], int (&prow)[kRows],
+                                                short (&pk0)[kRows], uint32_t (&xm)[kMarks], int a, int b) {
+  // the lane id laundered through a volatile move: keeps this rarely run
+  // code's lane-dependent addresses from being hoisted out of the shading
+  // loop (they would occupy registers, or scratch, for the whole loop)
+  int lane;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"((int)threadIdx.x));
+  if (blk.slot >= 0) {
+    KArg k = fresh();
+    double* row = k->split_rad + split_index(k, blk.slot) * k->spp * 3;
+    uint32_t* hw = k->split_hits + split_index(k, blk.slot) * ((k->spp + 31) >> 5);
+    for (int e = a + lane; e < b; e += 64) {
+      const int s = blk.s0 + hl.entry_id(e);  // one pixel: id = sample - s0
+      const int q = e & (kRound - 1);
+      if constexpr (kTail) {
+        if ((xm[q >> 5] >> (q & 31)) & 1u) continue;  // exported: its helper writes the sample
+      }
+      if constexpr (kTail) {  // (written through: read sc1 by the pixel's last contributor, maybe a helper)
+        st_wtd(row + 3 * s + 0, slot[q][0]);
+        st_wtd(row + 3 * s + 1, slot[q][1]);
+        st_wtd(row + 3 * s + 2, slot[q][2]);
+      } else {  // (combined in L2, written back by the release fence below)
+        row[3 * s + 0] = slot[q][0];
+        row[3 * s + 1] = slot[q][1];
+        row[3 * s + 2] = slot[q][2];
+      }
+      atomicOr(hw + (s >> 5), 1u << (s & 31));
+    }
+  } else {
+    const int P = blk.np, spp = blk.ns;
+    if (lane < P) {
+      const int a0 = lane * spp, a1 = a0 + spp;
+      int e0 = hl.off[a0 >> 5] + __popc(hl.bits[a0 >> 5] & ((1u << (a0 & 31)) - 1u));
+      int e1 = (a1 >> 5) < hl.nwords ? hl.off[a1 >> 5] + __popc(hl.bits[a1 >> 5] & ((1u << (a1 & 31)) - 1u)) : nh;
+      e0 = max(e0, a);
+      e1 = min(e1, b);
+      bool rowed = false;
+      if constexpr (kTail) rowed = prow[lane] >= 0;
+      if (rowed) {
+        // a pixel with exported paths (tail helpers): samples before its
+        // first exported one go to its running sum as below, the later
+        // ones (the exported ones aside: their helpers write them) to its
+        // row, which the pixel's last contributor sums in order
+        KArg k = fresh();
+        const int r = prow[lane], k0 = pk0[lane], bw = (k->spp_total + 31) >> 5;
+        double* row = k->tail_rows + (size_t)r * k->spp_total * 3;
+        uint32_t* hw = k->tail_bits + (size_t)r * bw;
+        double ax = psum[lane][0], ay = psum[lane][1], az = psum[lane][2];
+        for (int e = e0; e < e1; ++e) {
+          const int q = e & (kRound - 1);
+          if ((xm[q >> 5] >> (q & 31)) & 1u) continue;
+          const int sl = hl.entry_id(e) - a0;
+          if (sl < k0) {
+            ax += slot[q][0];
+            ay += slot[q][1];
+            az += slot[q][2];
+          } else {  // (written through: the row's last contributor reads it sc1)
+            st_wtd(row + 3 * sl + 0, slot[q][0]);
+            st_wtd(row + 3 * sl + 1, slot[q][1]);
+            st_wtd(row + 3 * sl + 2, slot[q][2]);
+            atomicOr(hw + (sl >> 5), 1u << (sl & 31));
+          }
+        }
+        psum[lane][0] = ax;
+        psum[lane][1] = ay;
+        psum[lane][2] = az;
+      } else if (e0 < e1) {
+        double ax = psum[lane][0], ay = psum[lane][1], az = psum[lane][2];
+        for (int e = e0; e < e1; ++e) {
+          const int q = e & (kRound - 1);
+          ax += slot[q][0];
+          ay += slot[q][1];
+          az += slot[q][2];
+        }
+        psum[lane][0] = ax;
+        psum[lane][1] = ay;
+        psum[lane][2] = az;
+      }
+    }
+  }
+}
+
+// ---- (kStream) the queue claim: the next chunk of the launch-wide queue,
+// [x, y) (empty: the cursor is past the last entry).  The wave claims entries
+// a chunk at a time (one relaxed add by one lane on the launch's cursor: a
+// claim per entry would put ~0.9 M adds per headline frame on one address).
+__device__ __forceinline__ uint2 stream_claim_chunk() {
+  const SArg sk = sfresh();
+  unsigned v = 0;
+  if (lane_now() == 0)
+    v = __hip_atomic_fetch_add(sk->s.cursor, (unsigned)sk->s.chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  v = __builtin_amdgcn_readfirstlane(v);
+  // (the cursor stays below 2^32: total < 2^31, and every wave adds
+  // at most one chunk of <= 2^16 entries past the end)
+  return make_uint2(min(v, sk->s.total), min(v + (unsigned)sk->s.chunk, sk->s.total));
+}
+// ... and the set-up of queue entry e: its camera ray and soft-shadow key
+// exactly as the block kernel's refill builds them (kBase: the frame's sample
+// sample_base + s, a progression's add); returns its row
+template <bool kBase>
+__device__ __forceinline__ int stream_entry(unsigned e, rt_rng& rng, d3& o, d3& d, uint64_t (&skey)[64]) {
+  const SArg sk = sfresh();
+  const unsigned spp = (unsigned)sk->k.spp, nlive = (unsigned)sk->s.nlive;
+  unsigned fl, i, s;
+  if (sk->s.order == 0) {
+    const unsigned t = e / spp;
+    s = e - t * spp;
+    fl = t / nlive;
+    i = t - fl * nlive;
+  } else {
+    const unsigned nf = (unsigned)sk->s.frames, t = e / nf;
+    fl = e - t * nf;
+    i = t / spp;
+    s = t - i * spp;
+  }
+  const int4 it = reinterpret_cast<const int4*>(sk->s.live)[i];
+  const uint64_t fkey = sk->k.frame_key[sk->s.frame0 + (int)fl];
+  Counters nc;
+  const unsigned fs = kBase ? (unsigned)sk->k.sample_base + s : s;
+  camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, sk->k.cf), sk->k.cf,
+                      it.x, it.y, (int)fs, rng, o, d, nc);
+  skey[lane_now()] = rt_soft_key(fkey, (uint32_t)it.y * (uint32_t)sk->k.W + (uint32_t)it.x, (uint32_t)fs);
+  return (int)((fl * spp + s) * nlive + i);
+}
+// ---- the block ring: the earliest entry still running (a wave-wide min over
+// the live lanes: swizzles within each half-wave, then the two halves' lane 0)
+__device__ __forceinline__ int ring_low(bool alive, int entry, int next) {
+  int lo = alive ? entry : next;
+  lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (16 << 10)));
+  lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (8 << 10)));
+  lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (4 << 10)));
+  lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (2 << 10)));
+  lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (1 << 10)));
+  return min(__builtin_amdgcn_readlane(lo, 0), __builtin_amdgcn_readlane(lo, 32));
+}
+// ... and the set-up of hit-list entry e: its camera ray (it hits: phase 1
+// found a hit for it) and soft-shadow key
+template <int kWords>
+__device__ __forceinline__ void block_entry(const HitList<kWords> hl, int e, rt_rng& rng, d3& o, d3& d, uint64_t (&skey)[64]) {
+  KArg k = fresh();
+  const BlockLoc loc = block_loc(k, block_of(k));
+  const int id = hl.entry_id(e), ns = loc.ns;
+  const int p = id / ns, s = k->sample_base + loc.s0 + id - p * ns;
+  const int tp = loc.p0 + p;
+  Counters nc;  // phase 1 counted this camera ray and its draws
+  const int px = loc.tx * 32 + (tp & 31), py = loc.ty * 32 + (tp >> 5);
+  camera_ray<false>(k, px, py, s, rng, o, d, nc);
+  skey[lane_now()] = rt_soft_key(k->frame_key[frame_of(k)], (uint32_t)py * (uint32_t)k->W + (uint32_t)px, (uint32_t)s);
+}
+
+// (kCount) the block's counters: wave reduction, then one atomic per counter
+__device__ __forceinline__ void reduce_counters(KArg k, int lane3, Counters c, Counters culled) {
+  for (int i = 0; i < 2 * kCounters; ++i) {
+    unsigned long long v = i < kCounters ? c.v[i] : culled.v[i - kCounters];
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    if (lane3 == 0) atomicAdd(&k->counts[i], v);
+  }
+}
+
 // kStream (render_stream_kernel): no blocks, no visibility
 // phase, no ring and no resolve -- the wave stages the scene once and then
 // takes entries (frame, live pixel, sample) off the launch-wide queue for as
@@ -1425,11 +1866,50 @@ __device__ __forceinline__ double (*tput_lds())[3] {
 // launch's scene has no triangle and no cube, which is every scene the auto
 // rule streams; the bounce code carries no triangle or cube test, mask, hit
 // field or select (Kind<kSph>).  The other instantiations keep their code.
-template <bool kCount, bool kStage, bool kPilot, bool kSky, bool kTailT, bool kStream = false, bool kBase = false,
-          bool kSph = false>
+//
+// A build of render_body is named by a variant type: the switches as named
+// members, one variant per kernel below.
+struct BodySwitches {  // (the defaults: a variant names only what it turns on)
+  static constexpr bool count = false;   // work counters (rt_counts)
+  static constexpr bool stage = false;   // the scene prefix staged into LDS
+  static constexpr bool pilot = false;   // a measuring render: per-pixel path lengths
+  static constexpr bool sky = false;     // a miss returns the opted-in sky
+  static constexpr bool tail = false;    // exports its last long paths to tail helpers
+  static constexpr bool stream = false;  // drains the launch-wide entry queue
+  static constexpr bool base = false;    // (stream) entry samples start at sample_base
+  static constexpr bool sph = false;     // (stream) the scene is spheres alone
+};
+template <bool kCount, bool kStage, bool kPilot, bool kSky>
+struct BlockBody : BodySwitches {  // render_kernel<kCount, kStage, kPilot, kSky>
+  static constexpr bool count = kCount, stage = kStage, pilot = kPilot, sky = kSky;
+};
+struct TailBody : BodySwitches {  // render_kernel_tail
+  static constexpr bool stage = true, tail = true;
+};
+struct StreamBody : BodySwitches {  // render_stream_kernel
+  static constexpr bool stage = true, stream = true;
+};
+struct StreamBaseBody : StreamBody {  // render_stream_base_kernel
+  static constexpr bool base = true;
+};
+struct StreamSphBody : StreamBody {  // render_stream_sph_kernel
+  static constexpr bool sph = true;
+};
+struct StreamSphBaseBody : StreamSphBody {  // render_stream_sph_base_kernel
+  static constexpr bool base = true;
+};
+template <class V>
+constexpr bool body_variant_ok() {
+  static_assert(!V::stream || (V::stage && !V::count && !V::pilot && !V::sky && !V::tail), "the stream kernel is the staged product body");
+  static_assert(!V::sph || V::stream, "spheres-only is a build of the stream kernel");
+  return true;
+}
+
+template <class V>
 __device__ __forceinline__ void render_body(const KParams& pk) {
-  static_assert(!kStream || (kStage && !kCount && !kPilot && !kSky && !kTailT), "the stream kernel is the staged product body");
-  static_assert(!kSph || kStream, "spheres-only is a build of the stream kernel");
+  static_assert(body_variant_ok<V>(), "");
+  constexpr bool kCount = V::count, kStage = V::stage, kPilot = V::pilot, kSky = V::sky, kStream = V::stream,
+                 kBase = V::base, kSph = V::sph;
   typedef typename Kind<kSph>::C CandK;
   typedef typename Kind<kSph>::H HitK;
   __shared__ uint32_t hbits[kStream ? 1 : kMaxBlockSamples / 32];  // hit samples of the block
@@ -1443,13 +1923,14 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
   // few long paths to the helpers past its main blocks.  The product kernel
   // has none of that code (compiled in but unused it cost 2-3 % one frame,
   // 1.5 % batched: r06 A/B)
-  constexpr bool kTail = kTailT && kStage && !kCount && !kPilot && !kSky;
+  constexpr bool kTail = V::tail && kStage && !kCount && !kPilot && !kSky;
 
   const int lane = threadIdx.x;
   int* stack = reinterpret_cast<int*>(dyn_lds + pk.stack_off) + lane;
   if constexpr (kTail) {
     if (pk.tail != nullptr && blockIdx.x - (unsigned)pk.tail_pos < (unsigned)pk.tail_helpers) {
       // a tail helper (launch_render adds them only with pk.tail set)
+      // (the staging loop, here and below, stays inline: "render_body's phases")
       const uint4* __restrict__ src = reinterpret_cast<const uint4*>(pk.stage_src);
       uint4* dst = reinterpret_cast<uint4*>(dyn_lds);
       for (int i = lane; i < pk.stage_bytes / 16; i += 64) dst[i] = src[i];
@@ -1498,22 +1979,13 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
   if constexpr (kCount) {
     for (int i = 0; i < kCounters; ++i) c.v[i] = culled.v[i] = 0;
   }
-#ifdef RT_WG_TIMING
-  if (lane < 16) solo_clk[lane] = 0;
-  const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-  unsigned long long dbg_iter = 0;
-  // wave-uniform section clocks (s_memtime): hit, lighting, soft; phase 1 (visibility)
-  unsigned long long dbg_hit = 0, dbg_light = 0, dbg_soft = 0, dbg_vis = 0;
-  // cone + hard shadow, scatter, lane-iterations alive, coop owners served, soft_seq passes
-  unsigned long long dbg_hard = 0, dbg_scat = 0, dbg_alive = 0, dbg_coop = 0, dbg_seq = 0;
-  // shade-iteration clocks and counts by live lanes: 1, 2, 3-4, 5-8, > 8
-  unsigned long long dbg_bclk[5] = {0, 0, 0, 0, 0}, dbg_bcnt[5] = {0, 0, 0, 0, 0}, dbg_bts = 0;
-  int dbg_bprev = -1;
-  const unsigned long long tv0 = __builtin_amdgcn_s_memtime();
-#endif
+  WgClock clk;
+  clk.start(lane);
   const CandK all = cand_all<kSph>();
 
   // ---- phase 1: visibility of the block's camera rays
+  // (inline, like the scan after it: a loop before the pass loop cannot leave
+  // this function, see "render_body's phases")
   if constexpr (!kStream) {
     // everything the loop needs is loaded once, before it (wave-uniform:
     // SGPRs); re-reading the kernarg segment inside the loop put scalar
@@ -1605,29 +2077,8 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
   }
   __syncthreads();
   const int nh = kStream ? 0 : hoff[nwords];
-  // sample id (pixel * ns + sample - s0) of hit-list entry e < nh: the bit
-  // word holding it (the last word whose list offset is <= e, by binary
-  // search over hoff), then the (e - offset)-th set bit of that word.  No
-  // materialized list: its 2 KB of LDS cost occupancy.
-  auto entry_id = [&](int e) -> int {
-    int w = 0;
-    for (int step = 16; step; step >>= 1)
-      if (w + step < nwords && hoff[w + step] <= e) w += step;
-    uint32_t word = hbits[w];
-    int k = e - hoff[w], pos = 0;
-    for (int sh = 16; sh; sh >>= 1) {
-      const int n = __popc(word & ((1u << sh) - 1u));
-      if (k >= n) {
-        k -= n;
-        word >>= sh;
-        pos += sh;
-      }
-    }
-    return w * 32 + pos;
-  };
-#ifdef RT_WG_TIMING
-  dbg_vis = __builtin_amdgcn_s_memtime() - tv0;
-#endif
+  const HitList<kStream ? 1 : kMaxBlockSamples / 32> hl{hbits, hoff, nwords};
+  clk.visibility_done();
 
   // ---- phases 2 + 3: shade the hit list through a RING of kRound radiance
   // slots (entry e -> slot e % kRound).  Paths finish out of order; the
@@ -1637,88 +2088,6 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
   // lanes keep taking entries until the ring is full (a barrier per batch of
   // kRound entries made every batch wait for its longest path).
   static_assert((kRound & (kRound - 1)) == 0, "kRound must be a power of two");
-  // adds entries [a, b) (all finished) to their pixels' sums in order; a
-  // split pixel's block stores them in its radiance slot row instead
-  auto resolve_entries = [&](int a, int b) {
-    // the lane id laundered through a volatile move: keeps this rarely run
-    // code's lane-dependent addresses from being hoisted out of the shading
-    // loop (they would occupy registers, or scratch, for the whole loop)
-    int lane;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"((int)threadIdx.x));
-    if (blk.slot >= 0) {
-      KArg k = fresh();
-      double* row = k->split_rad + split_index(k, blk.slot) * k->spp * 3;
-      uint32_t* hw = k->split_hits + split_index(k, blk.slot) * ((k->spp + 31) >> 5);
-      for (int e = a + lane; e < b; e += 64) {
-        const int s = blk.s0 + entry_id(e);  // one pixel: id = sample - s0
-        const int q = e & (kRound - 1);
-        if constexpr (kTail) {
-          if ((xm[q >> 5] >> (q & 31)) & 1u) continue;  // exported: its helper writes the sample
-        }
-        if constexpr (kTail) {  // (written through: read sc1 by the pixel's last contributor, maybe a helper)
-          st_wtd(row + 3 * s + 0, slot[q][0]);
-          st_wtd(row + 3 * s + 1, slot[q][1]);
-          st_wtd(row + 3 * s + 2, slot[q][2]);
-        } else {  // (combined in L2, written back by the release fence below)
-          row[3 * s + 0] = slot[q][0];
-          row[3 * s + 1] = slot[q][1];
-          row[3 * s + 2] = slot[q][2];
-        }
-        atomicOr(hw + (s >> 5), 1u << (s & 31));
-      }
-    } else {
-      const int P = blk.np, spp = blk.ns;
-      if (lane < P) {
-        const int a0 = lane * spp, a1 = a0 + spp;
-        int e0 = hoff[a0 >> 5] + __popc(hbits[a0 >> 5] & ((1u << (a0 & 31)) - 1u));
-        int e1 = (a1 >> 5) < nwords ? hoff[a1 >> 5] + __popc(hbits[a1 >> 5] & ((1u << (a1 & 31)) - 1u)) : nh;
-        e0 = max(e0, a);
-        e1 = min(e1, b);
-        bool rowed = false;
-        if constexpr (kTail) rowed = prow[lane] >= 0;
-        if (rowed) {
-          // a pixel with exported paths (tail helpers): samples before its
-          // first exported one go to its running sum as below, the later
-          // ones (the exported ones aside: their helpers write them) to its
-          // row, which the pixel's last contributor sums in order
-          KArg k = fresh();
-          const int r = prow[lane], k0 = pk0[lane], bw = (k->spp_total + 31) >> 5;
-          double* row = k->tail_rows + (size_t)r * k->spp_total * 3;
-          uint32_t* hw = k->tail_bits + (size_t)r * bw;
-          double ax = psum[lane][0], ay = psum[lane][1], az = psum[lane][2];
-          for (int e = e0; e < e1; ++e) {
-            const int q = e & (kRound - 1);
-            if ((xm[q >> 5] >> (q & 31)) & 1u) continue;
-            const int sl = entry_id(e) - a0;
-            if (sl < k0) {
-              ax += slot[q][0];
-              ay += slot[q][1];
-              az += slot[q][2];
-            } else {  // (written through: the row's last contributor reads it sc1)
-              st_wtd(row + 3 * sl + 0, slot[q][0]);
-              st_wtd(row + 3 * sl + 1, slot[q][1]);
-              st_wtd(row + 3 * sl + 2, slot[q][2]);
-              atomicOr(hw + (sl >> 5), 1u << (sl & 31));
-            }
-          }
-          psum[lane][0] = ax;
-          psum[lane][1] = ay;
-          psum[lane][2] = az;
-        } else if (e0 < e1) {
-          double ax = psum[lane][0], ay = psum[lane][1], az = psum[lane][2];
-          for (int e = e0; e < e1; ++e) {
-            const int q = e & (kRound - 1);
-            ax += slot[q][0];
-            ay += slot[q][1];
-            az += slot[q][2];
-          }
-          psum[lane][0] = ax;
-          psum[lane][1] = ay;
-          psum[lane][2] = az;
-        }
-      }
-    }
-  };
   if (kStream || nh > 0) {
     d3 o = mk(0, 0, 0), d = mk(0, 0, 0), T = mk(1, 1, 1);
     rt_rng rng{0};
@@ -1798,9 +2167,6 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
       int mi = 0, self = -1;
       HitK hs;
       int outer = 0;  // 1: continue the shade loop, 2: leave it
-#ifdef RT_WG_TIMING
-      unsigned long long ts0 = 0;
-#endif
       for (int pass = 0;; ++pass) {
         if constexpr (kStream) {
           // Lanes without a path take the next entries of the launch-wide
@@ -1813,15 +2179,9 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           for (int r = 0; r < 2 && fm != 0; ++r) {
             if (qbeg == qend) {
               if (dry) break;
-              const SArg sk = sfresh();
-              unsigned v = 0;
-              if (lane_now() == 0)
-                v = __hip_atomic_fetch_add(sk->s.cursor, (unsigned)sk->s.chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              v = __builtin_amdgcn_readfirstlane(v);
-              // (the cursor stays below 2^32: total < 2^31, and every wave adds
-              // at most one chunk of <= 2^16 entries past the end)
-              qbeg = min(v, sk->s.total);
-              qend = min(v + (unsigned)sk->s.chunk, sk->s.total);
+              const uint2 q = stream_claim_chunk();
+              qbeg = q.x;
+              qend = q.y;
               if (qbeg == qend) {
                 dry = true;
                 break;
@@ -1829,31 +2189,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             }
             const unsigned e = qbeg + (unsigned)lanes_below(fm);
             if (!alive && e < qend) {
-              const SArg sk = sfresh();
-              const unsigned spp = (unsigned)sk->k.spp, nlive = (unsigned)sk->s.nlive;
-              unsigned fl, i, s;
-              if (sk->s.order == 0) {
-                const unsigned t = e / spp;
-                s = e - t * spp;
-                fl = t / nlive;
-                i = t - fl * nlive;
-              } else {
-                const unsigned nf = (unsigned)sk->s.frames, t = e / nf;
-                fl = e - t * nf;
-                i = t / spp;
-                s = t - i * spp;
-              }
-              const int4 it = reinterpret_cast<const int4*>(sk->s.live)[i];
-              const uint64_t fkey = sk->k.frame_key[sk->s.frame0 + (int)fl];
-              Counters nc;
-              // the camera ray and the soft-shadow key exactly as the block
-              // kernel's refill below builds them (kBase: the frame's sample
-              // sample_base + s, a progression's add)
-              const unsigned fs = kBase ? (unsigned)sk->k.sample_base + s : s;
-              camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, sk->k.cf), sk->k.cf,
-                                  it.x, it.y, (int)fs, rng, o, d, nc);
-              skey[lane_now()] = rt_soft_key(fkey, (uint32_t)it.y * (uint32_t)sk->k.W + (uint32_t)it.x, (uint32_t)fs);
-              entry = (int)((fl * spp + s) * nlive + i);
+              entry = stream_entry<kBase>(e, rng, o, d, skey);
               set_path_T(mk(1, 1, 1));
               if constexpr (kSph) {
                 // (the zero made here: held in a register pair from the
@@ -1875,17 +2211,10 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
         if (freem != 0 && next == limit && next < nh) {
           // the ring is full and lanes are idle: sum every entry before the
           // earliest one still running (a wave-wide min over the live lanes)
-          // (swizzles within each half-wave, then the two halves' lane 0)
-          int lo = alive ? entry : next;
-          lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (16 << 10)));
-          lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (8 << 10)));
-          lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (4 << 10)));
-          lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (2 << 10)));
-          lo = min(lo, __builtin_amdgcn_ds_swizzle(lo, 0x1F | (1 << 10)));
-          lo = min(__builtin_amdgcn_readlane(lo, 0), __builtin_amdgcn_readlane(lo, 32));
+          const int lo = ring_low(alive, entry, next);
           if (lo > resolved) {
             __syncthreads();
-            resolve_entries(resolved, lo);
+            resolve_entries<kTail>(hl, nh, blk, slot, psum, prow, pk0, xm, resolved, lo);
             __syncthreads();
             if constexpr (kTail) {
               // the resolved entries' ring slots take new entries now: their
@@ -1905,15 +2234,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
         // lanes without a path take the next entries, in lane order
         const int e = next + lanes_below(freem);
         if (!kStream && !alive && e < limit) {
-          KArg k = fresh();
-          const BlockLoc loc = block_loc(k, block_of(k));
-          const int id = entry_id(e), ns = loc.ns;
-          const int p = id / ns, s = k->sample_base + loc.s0 + id - p * ns;
-          const int tp = loc.p0 + p;
-          Counters nc;  // phase 1 counted this camera ray and its draws
-          const int px = loc.tx * 32 + (tp & 31), py = loc.ty * 32 + (tp >> 5);
-          camera_ray<false>(k, px, py, s, rng, o, d, nc);
-          skey[lane_now()] = rt_soft_key(k->frame_key[frame_of(k)], (uint32_t)py * (uint32_t)k->W + (uint32_t)px, (uint32_t)s);
+          block_entry(hl, e, rng, o, d, skey);
           entry = e;
           T = mk(1, 1, 1);
           set_path_L(mk(0, 0, 0));
@@ -1928,21 +2249,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             outer = (kStream ? dry : next >= nh) ? 2 : 1;
             break;
           }
-#ifdef RT_WG_TIMING
-          ++dbg_iter;
-          dbg_alive += __popcll(__ballot(alive));
-          {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            if (dbg_bprev >= 0) dbg_bclk[dbg_bprev] += now - dbg_bts;
-            const int nal = __popcll(__ballot(alive));
-            dbg_bprev = nal == 1 ? 0 : (nal == 2 ? 1 : (nal <= 4 ? 2 : (nal <= 8 ? 3 : 4)));
-            dbg_bcnt[dbg_bprev] += 1;
-            dbg_bts = now;
-          }
-          if (dbg_iter % 4 == 0 && dbg_iter / 4 < 16 && lane == 0 && fresh()->dbg)
-            fresh()->dbg[(size_t)blockIdx.x * kDbgStride + 16 + dbg_iter / 4] = __builtin_amdgcn_s_memrealtime();
-          ts0 = __builtin_amdgcn_s_memtime();
-#endif
+          clk.iteration(alive, lane);
           if constexpr (kTail) {
             // Tail helpers: every entry has started and at
             // most tail_kmax paths are left, each tail_dmin bounces deep or
@@ -1967,27 +2274,12 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
                   const unsigned long long t_x = __builtin_amdgcn_s_memrealtime();
                   KArg k = fresh();
                   TailCtl* ctl = k->tail;
-                  int idx = -1;
-                  // a helper for it (paths in flight < live helpers: the gate word is
-                  // read first, so draining waves do not add to it in vain) and a
-                  // queue entry
-                  if (lane == 0) {
-                    const unsigned long long g0 = __hip_atomic_load(ctl->gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((uint32_t)g0 < (uint32_t)(g0 >> 32)) {
-                      const unsigned long long g = atomicAdd(ctl->gate, 1ull);
-                      if ((uint32_t)g < (uint32_t)(g >> 32)) {
-                        const unsigned int t = atomicAdd(ctl->tail, 1u);
-                        if (t < (unsigned int)k->tail_cap) idx = (int)t;  // (entries past the cap are never taken)
-                      }
-                      if (idx < 0) atomicAdd(ctl->gate, ~0ull);
-                    }
-                  }
-                  idx = __builtin_amdgcn_readfirstlane(idx);
+                  const int idx = tail_reserve(k);
                   // (all the handed-over bytes below are written through: st_wt*)
                   if (idx < 0) break;  // (no helper free: the paths stay here)
                   const int e = (int)rl32((uint32_t)entry, ow);
                   const BlockLoc loc = block_loc(k, block_of(k));
-                  const int id = entry_id(e), ns = loc.ns;
+                  const int id = hl.entry_id(e), ns = loc.ns;
                   const int p = id / ns, sl = id - p * ns;
                   const int tp = loc.p0 + p;
                   const int px = loc.tx * 32 + (tp & 31), py = loc.ty * 32 + (tp >> 5);
@@ -2002,25 +2294,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
                   } else {
                     kind = kTailRow;
                     sample = sl;
-                    int r = prow[p];
-                    if (r < 0) {  // the pixel's dynamic row (one row per export at most: rows_used < cap)
-                      if (lane == 0) r = (int)atomicAdd(ctl->rows_used, 1u);
-                      r = __builtin_amdgcn_readfirstlane(r);
-                      const int bw = (k->spp_total + 31) >> 5;
-                      for (int w = lane; w < bw; w += 64) st_wt32(k->tail_bits + (size_t)r * bw + w, 0u);
-                      if (lane == 0) {
-                        TailRow* hd = k->tail_hdr + r;
-                        st_wt32(&hd->counter, 2u);  // the block's own share (given back in its epilogue) + this path
-                        st_wt32(&hd->k0, (uint32_t)sl);
-                        st_wt32(&hd->frame, (uint32_t)frame_of(k));
-                        st_wt64(&hd->oi, (uint64_t)oi);
-                        prow[p] = r;
-                        pk0[p] = (short)sl;
-                      }
-                    } else if (lane == 0) {
-                      pk0[p] = (short)min((int)pk0[p], sl);
-                      atomicAdd(&k->tail_hdr[r].counter, 1);  // one more path owes the row a sample
-                    }
+                    const int r = tail_pixel_row(k, p, sl, oi, prow, pk0);
                     row = r;
                   }
                   if (lane == ow) {
@@ -2114,13 +2388,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             if constexpr (kSky) {  // an opted-in sky instead of black (rt_settings.sky)
               if (missed) set_path_L(path_L() + mul(T, sky_color(fresh()->sky, d)));
             }
-            if constexpr (kPilot) {  // a measuring render: the pixel's longest path and its bounces
-              KArg k = fresh();
-              const BlockLoc loc = block_loc(k, block_of(k));
-              const size_t px = (size_t)loc.lt * 1024 + loc.p0 + entry_id(entry) / loc.ns;
-              atomicMax(k->work_max + px, (unsigned)depth + 1u);
-              atomicAdd(k->work_sum + px, (unsigned)depth + 1u);
-            }
+            if constexpr (kPilot) pilot_record(hl, entry, depth);
             stream_store_row();
             alive = false;  // finished: its radiance is in its slot, the lane is free for the second pass
           } else {
@@ -2157,11 +2425,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
       if (outer == 1) continue;
       if (outer == 2) break;
 
-#ifdef RT_WG_TIMING
-      const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
-      dbg_hit += ts1 - ts0;
-#endif
-
+      clk.hit_done();
       if (__ballot(shade) != 0) {
         // (2) calculateDirectLighting (renderer.go:229-297), light by light
         const Hot h = hot<kStage, kSph>();
@@ -2176,9 +2440,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           double ldist = 0;
           CandK cm{};
           bool lit = false, occl = false;
-#ifdef RT_WG_TIMING
-          const unsigned long long th0 = __builtin_amdgcn_s_memtime();
-#endif
+          clk.begin(kClkHard);
           if (shade) {
             d3 lv = ld3(Lt.pos) - P;
             ldist = sqrt(lv.x * lv.x + lv.y * lv.y + lv.z * lv.z);
@@ -2223,9 +2485,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               occl = shadow_blocked<kCount, kSph>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray
             }
           }
-#ifdef RT_WG_TIMING
-          dbg_hard += __builtin_amdgcn_s_memtime() - th0;
-#endif
+          clk.end(kClkHard);
           const bool need_soft = lit && !occl && soft;
           // the 16 soft rays are traced unless their shadow cone is empty or
           // the light is inert (dark: the shading is the same whatever they hit)
@@ -2257,13 +2517,9 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           rt_rng srng{traced_soft ? rt_soft_state(skey[lane_now()], (uint32_t)depth, (uint32_t)li) : 0ull};
           // soft shadows: wave-converged decision between the two forms
           const unsigned long long owners = __ballot(traced_soft);
-#ifdef RT_WG_TIMING
-          const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
-#endif
+          clk.begin(kClkSoft);
           if (owners != 0) {
-#ifdef RT_WG_TIMING
-            if (__popcll(owners) <= kCoopMax) dbg_coop += __popcll(owners); else ++dbg_seq;
-#endif
+            clk.soft_form(owners);
             // cooperative soft shadows when at most kCoopMax lanes need them
             if (__popcll(owners) <= kCoopMax) {
               for (unsigned long long b = owners; b; b &= b - 1) {
@@ -2283,9 +2539,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               if (traced_soft) unocc = uq;  // (a free lane keeps its 16)
             }
           }
-#ifdef RT_WG_TIMING
-          dbg_soft += __builtin_amdgcn_s_memtime() - ts2;
-#endif
+          clk.end(kClkSoft);
           if (lit) {
             const double sf = occl ? 0.0 : (soft ? (double)unocc / 16.0 : 1.0);  // shadowSum / 16
             if (sf > 0.0) {
@@ -2304,13 +2558,9 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             }
           }
         }
-#ifdef RT_WG_TIMING
-        dbg_light += __builtin_amdgcn_s_memtime() - ts1;
-#endif
+        clk.end(kClkLight);
         // (3) Material.Scatter and the traceRay combination (renderer.go:181-226)
-#ifdef RT_WG_TIMING
-        const unsigned long long tc0 = __builtin_amdgcn_s_memtime();
-#endif
+        clk.begin(kClkScat);
         if (shade) {
           d3 E = ld3(m->emit);
           const Scat sc = scatter<kCount>(m, d, N, front, rng, c);
@@ -2328,25 +2578,17 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             }
           }
         }
-#ifdef RT_WG_TIMING
-        dbg_scat += __builtin_amdgcn_s_memtime() - tc0;
-#endif
+        clk.end(kClkScat);
       }
       if (fin) {  // the path's radiance goes to its entry's ring slot
-        if constexpr (kPilot) {  // a measuring render: the pixel's longest path and its bounces
-          KArg k = fresh();
-          const BlockLoc loc = block_loc(k, block_of(k));
-          const size_t px = (size_t)loc.lt * 1024 + loc.p0 + entry_id(entry) / loc.ns;
-          atomicMax(k->work_max + px, (unsigned)depth + 1u);
-          atomicAdd(k->work_sum + px, (unsigned)depth + 1u);
-        }
+        if constexpr (kPilot) pilot_record(hl, entry, depth);
         stream_store_row();
         alive = false;  // (its radiance is in its slot already)
       }
     }
     if constexpr (!kStream) {
       __syncthreads();
-      resolve_entries(resolved, nh);
+      resolve_entries<kTail>(hl, nh, blk, slot, psum, prow, pk0, xm, resolved, nh);
       __syncthreads();
     }
   }
@@ -2356,37 +2598,11 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
 #undef set_path_T
 #undef path_q
 #undef stream_store_row
-#ifdef RT_WG_TIMING
-  const unsigned long long t_loop = __builtin_amdgcn_s_memrealtime();
-  if (dbg_bprev >= 0) dbg_bclk[dbg_bprev] += __builtin_amdgcn_s_memtime() - dbg_bts;
-#endif
+  clk.loop_done();
   if constexpr (kStream) {
     // every row of this wave's paths is written; resolve_rows_kernel, the next
     // kernel on the stream, sums them
-#ifdef RT_WG_TIMING
-    if (fresh()->dbg && threadIdx.x == 0) {  // the block kernel's record (below), without a block
-      unsigned long long* r = fresh()->dbg + (size_t)blockIdx.x * kDbgStride;
-      r[0] = t_start;
-      r[1] = t_loop;
-      r[2] = __builtin_amdgcn_s_memrealtime();
-      r[3] = dbg_hit;
-      r[4] = dbg_light;
-      r[5] = dbg_soft;
-      r[6] = dbg_vis;
-      r[7] = dbg_iter;
-      r[8] = dbg_hard;
-      r[9] = dbg_scat;
-      r[10] = dbg_alive;
-      r[11] = dbg_coop;
-      r[12] = dbg_seq;
-      r[13] = r[14] = 0;
-      for (int i = 0; i < 5; ++i) {
-        r[32 + i] = dbg_bclk[i];
-        r[37 + i] = dbg_bcnt[i];
-      }
-      r[42] = r[43] = 0;
-    }
-#endif
+    clk.stream_write(threadIdx.x);
     return;
   }
 
@@ -2467,68 +2683,9 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
       }
     }
   }
-  if constexpr (kTail) {
-    // pixels with exported paths: the block gives back its share of each
-    // row (the running sum of the samples before the row's first one), and
-    // the row's last contributor sums it and writes the pixel
-    if (k->tail != nullptr && blk.slot < 0) {
-      int last = 0;
-      if (prow[lane3] >= 0) {
-        TailRow* hd = k->tail_hdr + prow[lane3];
-        st_wtd(hd->prefix, psum[lane3][0]);
-        st_wtd(hd->prefix + 1, psum[lane3][1]);
-        st_wtd(hd->prefix + 2, psum[lane3][2]);
-        st_wt32(&hd->k0, (uint32_t)pk0[lane3]);
-      }
-      wt_drain();  // (the resolve's row samples too) before the counter
-      if (prow[lane3] >= 0) last = atomicSub(&k->tail_hdr[prow[lane3]].counter, 1) == 1 ? 1 : 0;
-      for (unsigned long long b = __ballot(last); b; b &= b - 1) {
-        const int r = prow[__builtin_ctzll(b)], spp = k->spp_total, bw = (spp + 31) >> 5;
-        const TailRow* hd = k->tail_hdr + r;
-        double a = lane3 < 3 ? ld_wtd(hd->prefix + lane3) : 0.0;
-        a = row_sum<true>(slot, k->tail_rows + (size_t)r * spp * 3, k->tail_bits + (size_t)r * bw, (int)ld_wt32(&hd->k0),
-                          spp, a, lane3);
-        const double sx = rld(a, 0), sy = rld(a, 1), sz = rld(a, 2);
-        if (lane3 == 0) store_pixel(k, (int)ld_wt32(&hd->frame), (size_t)ld_wt64(&hd->oi), sx, sy, sz);
-      }
-    }
-  }
-  if constexpr (kCount) {
-    for (int i = 0; i < 2 * kCounters; ++i) {
-      // wave reduction, then one atomic per counter
-      unsigned long long v = i < kCounters ? c.v[i] : culled.v[i - kCounters];
-      for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-      if (lane3 == 0) atomicAdd(&k->counts[i], v);
-    }
-  }
-#ifdef RT_WG_TIMING
-  if (k->dbg && lane3 == 0) {
-    unsigned long long* r = k->dbg + (size_t)blockIdx.x * kDbgStride;
-    r[0] = t_start;
-    r[1] = t_loop;
-    r[2] = __builtin_amdgcn_s_memrealtime();
-    r[3] = dbg_hit;
-    r[4] = dbg_light;
-    r[5] = dbg_soft;
-    r[6] = dbg_vis;
-    r[7] = dbg_iter;
-    r[8] = dbg_hard;
-    r[9] = dbg_scat;
-    r[10] = dbg_alive;
-    r[11] = dbg_coop;
-    r[12] = dbg_seq;
-    r[13] = (unsigned long long)blk.np * 65536ull + (unsigned long long)blk.ns;
-    r[14] = (unsigned long long)(blk.slot + 1);
-    for (int i = 0; i < 5; ++i) {
-      r[32 + i] = dbg_bclk[i];
-      r[37 + i] = dbg_bcnt[i];
-    }
-    if (solo_clk[6])  // a lone path ran: its section clocks replace the iteration stamps
-      for (int i = 0; i < 16; ++i) r[16 + i] = solo_clk[i];
-    r[42] = solo_clk[6];  // lone-path bounces (0: none ran)
-    r[43] = solo_clk[7];  // entries into solo_path
-  }
-#endif
+  if constexpr (kTail) tail_rows_give_back(k, blk, lane3, slot, psum, prow, pk0);
+  if constexpr (kCount) reduce_counters(k, lane3, c, culled);
+  clk.write(k, lane3, true, (unsigned long long)blk.np * 65536ull + (unsigned long long)blk.ns, (unsigned long long)(blk.slot + 1));
   if constexpr (kTail) {
     if (k->tail != nullptr) {
       // this main block is done: it queues nothing more (no fence: its queue
@@ -2539,31 +2696,31 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
 }
 template <bool kCount, bool kStage, bool kPilot, bool kSky>
 __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_kernel(const KParams pk) {
-  render_body<kCount, kStage, kPilot, kSky, false>(pk);
+  render_body<BlockBody<kCount, kStage, kPilot, kSky>>(pk);
 }
 // the staged product render with tail helpers (rt_tuning.tail_helpers > 0)
 __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_kernel_tail(const KParams pk) {
-  render_body<false, true, false, false, true>(pk);
+  render_body<TailBody>(pk);
 }
 
 // ---- streamed launches
 // One persistent one-wave workgroup per resident wave slot; each drains the
-// launch-wide entry queue (render_body<kStream>).
+// launch-wide entry queue (render_body<StreamBody> and its three siblings).
 __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_stream_kernel(const StreamKArgs a) {
-  render_body<false, true, false, false, false, true>(a.k);
+  render_body<StreamBody>(a.k);
 }
 // The same with KParams::sample_base added to every entry's sample index (a
 // progression's adds after its first).
 __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_stream_base_kernel(const StreamKArgs a) {
-  render_body<false, true, false, false, false, true, true>(a.k);
+  render_body<StreamBaseBody>(a.k);
 }
 // The two for a scene of spheres alone (kSph; launch_stream picks them), with
 // a waves-per-SIMD bound of their own.
 __global__ __launch_bounds__(64, RT_STREAM_SPH_WAVES) void render_stream_sph_kernel(const StreamKArgs a) {
-  render_body<false, true, false, false, false, true, false, true>(a.k);
+  render_body<StreamSphBody>(a.k);
 }
 __global__ __launch_bounds__(64, RT_STREAM_SPH_WAVES) void render_stream_sph_base_kernel(const StreamKArgs a) {
-  render_body<false, true, false, false, false, true, true, true>(a.k);
+  render_body<StreamSphBaseBody>(a.k);
 }
 // After it on the same stream: one lane per pixel of the rank's tiles, per
 // frame of the launch (blockIdx.y).  Lane t writes local pixel t black when it
@@ -2639,18 +2796,23 @@ int stream_wave_slots(int device, int kernel, size_t shmem) {
   return pr.multiProcessorCount * per_cu;
 }
 
+// A launch of one frame: frame entry 0 from the single-frame fields
+// (launch_stream, launch_render)
+static void single_frame_entry(KParams& p) {
+  if (p.nframes > 1) return;
+  p.nframes = 1;
+  p.frame_key[0] = p.seed_key;
+  p.frame_lin[0] = p.out_linear;
+  p.frame_rgba[0] = p.out_rgba;
+}
+
 int launch_stream(const KParams& pin, const StreamParams& sp, int wgs, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   StreamKArgs a;
   a.k = pin;
   a.s = sp;
   KParams& p = a.k;
-  if (p.nframes <= 1) {  // one frame: entry 0 from the single-frame fields (as launch_render)
-    p.nframes = 1;
-    p.frame_key[0] = p.seed_key;
-    p.frame_lin[0] = p.out_linear;
-    p.frame_rgba[0] = p.out_rgba;
-  }
+  single_frame_entry(p);
   p.tail = nullptr;
   if (p.stage_bytes <= 0 || p.use_bvh || wgs <= 0 || sp.frames <= 0 || sp.npix <= 0) return (int)hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(sp.cursor, 0, sizeof(unsigned int), st);
@@ -2826,12 +2988,7 @@ int launch_render(const KParams& pin, bool count, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (pin.num_wgs <= 0) return hipSuccess;
   KParams p = pin;
-  if (p.nframes <= 1) {  // one frame: entry 0 from the single-frame fields
-    p.nframes = 1;
-    p.frame_key[0] = p.seed_key;
-    p.frame_lin[0] = p.out_linear;
-    p.frame_rgba[0] = p.out_rgba;
-  }
+  single_frame_entry(p);
   const size_t shmem = render_shmem(p);
   const bool stage = p.stage_bytes > 0;
   // tail helpers: render_kernel_tail exports paths;
