@@ -73,6 +73,16 @@ constexpr int kDefaultLeaf = 4;   // spheres per leaf at most (C4: 872 ms at 2, 
 
 }  // namespace
 
+// A sphere with a non-finite centre or radius has no box: Sphere.Hit accepts
+// every ray at t = NaN for a NaN one (sphere.go: no comparison with NaN
+// rejects), which only the linear scan reproduces; and the builder's bin
+// index, padding and quantization assume finite bounds.
+bool spheres_finite(const FlatScene& fs) {
+  for (const DSphere& s : fs.spheres)
+    if (!std::isfinite(s.c[0] + s.c[1] + s.c[2] + s.r)) return false;
+  return true;
+}
+
 void build_sphere_bvh(FlatScene* fs, int bins, int leaf) {
   // rt_tuning: bins, leaf (<= 7: a 3-bit count); 0 = the defaults
   const int kBins = bins > 0 ? std::max(2, std::min(kMaxBins, bins)) : kDefaultBins;
@@ -83,7 +93,7 @@ void build_sphere_bvh(FlatScene* fs, int bins, int leaf) {
   fs->bvh4_stack = 0;
   fs->bvh4_root = 0;
   const int n = (int)fs->spheres.size();
-  if (n == 0) return;
+  if (n == 0 || !spheres_finite(*fs)) return;  // (no BVH: the scene keeps the linear scan)
   std::vector<Box> pb(n);
   std::vector<double> cen(3 * (size_t)n);
   double M = 1.0;

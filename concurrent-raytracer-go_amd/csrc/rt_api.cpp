@@ -42,6 +42,28 @@ static int validate_scene(const rt_scene* s) {
       return RT_E_INVALID;
     }
   }
+  // Non-finite geometry (rt_api.h, rt_context_set_scene): spheres alone are
+  // rendered as the reference renders them; a cube with a non-finite position
+  // or size, and a non-finite sphere in a scene that has cubes, are refused
+  // (the closest hit scans spheres before triangles, which equals the
+  // reference's hittable order only while the closest distance is not NaN).
+  bool cubes = false;
+  for (int i = 0; i < s->num_objects; ++i) cubes = cubes || s->objects[i].type == RT_OBJ_CUBE;
+  for (int i = 0; i < s->num_objects && cubes; ++i) {
+    const rt_object& o = s->objects[i];
+    const char* field = nullptr;
+    for (int k = 0; k < 3 && !field; ++k) {
+      if (!std::isfinite(o.position[k])) field = "position";
+      else if (o.type == RT_OBJ_CUBE && !std::isfinite(o.size[k])) field = "size";
+    }
+    if (!field && o.type == RT_OBJ_SPHERE && !std::isfinite(o.radius)) field = "radius";
+    if (field) {
+      set_error("object " + std::to_string(i) + ": " + (o.type == RT_OBJ_CUBE ? "cube " : "sphere ") + field +
+                " is not finite" + (o.type == RT_OBJ_CUBE ? "" : " in a scene with cubes") +
+                " (non-finite geometry is rendered for spheres alone)");
+      return RT_E_INVALID;
+    }
+  }
   return RT_OK;
 }
 
@@ -358,7 +380,9 @@ int rt_context_set_scene(rt_context* c, const rt_scene* s, int32_t force_bvh) {
   c->prog_on = false;  // (a progression ends with its scene)
   flatten_scene(*s, &c->flat);
   c->bvh_seconds = 0;
-  const bool want_bvh = force_bvh > 0 || (force_bvh == 0 && c->flat.spheres.size() > 64);
+  // (a sphere with a non-finite centre or radius: no BVH, even when forced; rt_api.h)
+  const bool want_bvh =
+      (force_bvh > 0 || (force_bvh == 0 && c->flat.spheres.size() > 64)) && spheres_finite(c->flat);
   if (want_bvh && !c->flat.tris.empty()) {
     if (force_bvh > 0) {
       set_error("BVH supports sphere-only scenes");
@@ -427,7 +451,10 @@ int rt_context_set_scene(rt_context* c, const rt_scene* s, int32_t force_bvh) {
   // (the 1 KB PCG jump table stays in global memory, L1-cached: only the
   // cooperative soft-shadow form reads it, and scenes near the LDS limit of 12
   // workgroups per CU ran faster without it)
-  c->stage_bytes = (f.bvh.empty() && off_j <= 48 * 1024) ? (int32_t)off_j : 0;
+  // (not with a non-finite sphere: the staged kernels' wide mode splits the
+  // closest-hit scan among helper lanes and merges by distance, closest_wide,
+  // which equals the sequential scan only while no hit distance is NaN)
+  c->stage_bytes = (f.bvh.empty() && off_j <= 48 * 1024 && spheres_finite(f)) ? (int32_t)off_j : 0;
   c->have_scene = true;
   c->scene_gen += 1;
   return RT_OK;

@@ -375,6 +375,86 @@ __device__ __forceinline__ typename Kind<kSph>::C cand_all() {  // every primiti
   return m;
 }
 
+// ------------------------------------------------------------ path radiance
+// A path's radiance is carried forward, L += T * c_k with the throughput
+// T = prod(a_j * rw_j), where traceRay recurses: X_k = c_k + (a_k * X_{k+1}) *
+// rw_k (renderer.go:181-226; black, X = 0, at a miss, at the depth cut-off and
+// without recursion).  The two agree while every a_k is finite.  After an
+// attenuation that is not (an infinite or NaN colour component) the
+// reference's channel is a_q * X_{q+1} whatever came before it: NaN when the
+// rest of the path adds up to 0 (Inf * 0: the next ray misses) or to NaN, else
+// an infinity of the product's sign.  So, per channel: when the throughput
+// stops being finite, L restarts at 0 and T becomes a marker -- 2^600 with the
+// throughput's sign, or NaN -- under which the rest of the path accumulates as
+// before (scaled by 2^600, far from overflow); at the path's end a marked
+// channel is its sum times +Inf (path_end).  (A marker is |T| >= 2^500 or
+// NaN: finite colours beyond 1e150 are not served; a zero attenuation after
+// the marker loses it.)  A sum that is NaN already (c_q itself: an infinite
+// albedo times a zero cosine) stays NaN whatever follows: the marker is NaN.
+__device__ __forceinline__ void path_restart(double& t, double& l) {
+  if (!__builtin_isfinite(t)) {
+    t = (t != t || l != l) ? __builtin_nan("") : __builtin_copysign(0x1p600, t);
+    l = 0.0;
+  }
+}
+// T *= a * rw (the same product as before), then the restart where it applies
+__device__ __forceinline__ void path_step(d3& T, d3& L, d3 A, double rw) {
+  T = mul(T, muls(A, rw));
+  if (!__builtin_isfinite((T.x + T.y) + T.z)) {
+    path_restart(T.x, L.x);
+    path_restart(T.y, L.y);
+    path_restart(T.z, L.z);
+  }
+}
+__device__ __forceinline__ double path_end1(double l, double t) {
+  return fabs(t) < 0x1p500 ? l : l * (fabs(t) * __builtin_inf());
+}
+// the radiance of a finished path from its sum and its last throughput
+__device__ __forceinline__ d3 path_end(d3 L, d3 T) {
+  if (!((fabs(T.x) + fabs(T.y)) + fabs(T.z) < 0x1p500))
+    L = mk(path_end1(L.x, T.x), path_end1(L.y, T.y), path_end1(L.z, T.z));
+  return L;
+}
+
+// A BVH only serves finite rays.  Sphere.Hit accepts what it cannot compare:
+// with a NaN or infinite component in the origin or the direction, `disc < 0`
+// and `root < tMin || tMax < root` (sphere.go:22-40) are false for spheres far
+// from any line, while a slab test of such a ray rejects boxes (a NaN slab is
+// ignored, an infinite direction's inverse is 0).  Such a ray is tested
+// against every sphere instead (closest_scan, any_hit's linear scan).  (The
+// sum overflowing for finite values only costs the scan.)
+__device__ __forceinline__ bool ray_finite(d3 o, d3 d) {
+  return __builtin_isfinite(((o.x + o.y) + (o.z + d.x)) + (d.y + d.z));
+}
+
+// hitWorld's closest hit of a non-finite ray over the spheres of a BVH scene,
+// whose array order is the BVH's, not the hittable order.  The sequential scan
+// lets every accepted hittable replace the one before it; an accepted hit of
+// such a ray is not nearer than the closest so far (t is NaN), so the scan
+// ends with the last accepted hittable: here, the largest hittable index
+// among the hits that are not strictly nearer.
+template <bool kCount, bool kSph>
+__device__ __forceinline__ bool closest_scan(const Geo& p, d3 o, d3 d, double a, double inv_a,
+                                             typename Kind<kSph>::H& hs, Counters& c) {
+  double closest = __builtin_inf();
+  int best_obj = -1;
+  for (int i = 0; i < p.ns; ++i) {
+    cnt<kCount>(c, C_SPH);
+    const DSphere& S = p.spheres[i];
+    double num;
+    if (sphere_query(S, o, d, a, inv_a, 0.001, closest, num)) {
+      const double t = num / a;
+      if (!(t < closest) && best_obj > S.obj) continue;
+      closest = t;
+      hs.num = num;
+      hs.idx = i;
+      if constexpr (!kSph) hs.is_tri = 0;
+      best_obj = S.obj;
+    }
+  }
+  return best_obj >= 0;
+}
+
 // hitWorld closest hit, renderer.go:333-346.  Linear scan in hittable order
 // (spheres before triangles; an exact-t tie is resolved by hittable index so
 // the later hittable wins, as in Go), or BVH traversal with the same rule.
@@ -387,6 +467,7 @@ __device__ __forceinline__ bool closest_hit(const Geo& p, d3 o, d3 d, typename K
   int best_obj = -1;
   const double a = len2(d);
   const double inv_a = approx_rcp(a);
+  if (p.use_bvh && !ray_finite(o, d)) return closest_scan<kCount, kSph>(p, o, d, a, inv_a, hs, c);
   if (p.use_bvh) {
     const d3 id = inv_dir(d);
     int sp = 0;
@@ -495,7 +576,8 @@ __device__ __forceinline__ bool any_hit(const Geo& p, d3 o, d3 d, double tmax, i
   const double tmin = 0.001;
   const double a = len2(d);
   const double inv_a = approx_rcp(a);
-  if (p.use_bvh) {
+  // (a non-finite ray: no box can be trusted, every sphere gets its exact test; ray_finite)
+  if (p.use_bvh && ray_finite(o, d)) {
     const d3 id = inv_dir(d);
     int sp = 0;
     cnt<kCount>(c, C_BOX);

@@ -73,7 +73,10 @@ void sky_presets(DSky out[kSkies]);
 void flatten_scene(const rt_scene& s, FlatScene* out);
 // Binned-SAH BVH over out->spheres (reorders spheres). Requires no triangles.
 // bins / leaf: SAH bins per axis and spheres per leaf at most (0: defaults).
+// Leaves fs->bvh empty (the linear scan) when !spheres_finite(*fs).
 void build_sphere_bvh(FlatScene* fs, int bins, int leaf);
+// Every sphere's centre and radius is finite (a BVH can hold it).
+bool spheres_finite(const FlatScene& fs);
 // The global tiles a rank renders, in local-tile order (local tile lt is
 // tiles[lt]): t % world == rank (strided, createRenderTasks order dealt
 // round-robin) or a partition's list (rt_partition, rt_multi.cpp).

@@ -143,12 +143,17 @@ __device__ __forceinline__ bool in_cone(const double* cc, double r, d3 P, d3 ldi
   const double dc2 = len2(v);
   const double dc = (double)__builtin_amdgcn_sqrtf((float)dc2);
   const double ra = fabs(r) * KC(1.0 + 1e-5) + KC(1e-5) * dc + KC(1e-12);  // inflated radius
-  const bool inside = dc <= ra;                                           // P inside / on it
+  // Every test is "not provably missed": a NaN hit point, light direction,
+  // centre or radius fails each comparison and the sphere is kept, as
+  // Sphere.Hit accepts what it cannot compare (`disc < 0`, `root < tMin ||
+  // tMax < root` are false for NaN, sphere.go:22-40), so a NaN shadow ray is
+  // blocked by every sphere
+  const bool inside = !(dc > ra);                                         // P inside / on it
   const bool beyond = dc - ra > ldist * KC(1.0 + 1e-5) + KC(1e-9);      // beyond the light
   // angle(v, ldir) <= alpha + beta, sin(alpha) = 0.1, sin(beta) = ra/dc:
   // v.ldir >= dc*cos(alpha+beta) = cos(alpha)*sqrt(dc^2-ra^2) - 0.1*ra
   const double tl = (double)__builtin_amdgcn_sqrtf((float)fmax(dc2 - ra * ra, 0.0));
-  const bool meets = dot(v, ldir) >= KC(0.99498) * tl - KC(0.1) * ra - KC(1e-5) * dc;
+  const bool meets = !(dot(v, ldir) < KC(0.99498) * tl - KC(0.1) * ra - KC(1e-5) * dc);
   return inside || (!beyond && meets);
 }
 
@@ -1007,7 +1012,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
     const Geo& g = h.g;
     if (depth >= h.max_depth) {  // traceRay depth cut-off: contributes 0
       if (dep_out) *dep_out = depth;
-      return L;
+      return path_end(L, T);
     }
     clk.solo_count(6);
     // (1) closest hit (hitWorld, renderer.go:170)
@@ -1017,7 +1022,7 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
     if (!found) {  // miss -> black (or the opted-in sky)
       if constexpr (kSky) L = L + mul(T, sky_color(launder(karg)->sky, d));
       if (dep_out) *dep_out = depth + 1;
-      return L;
+      return path_end(L, T);
     }
     d3 P, N;
     bool front;
@@ -1245,14 +1250,14 @@ __device__ RT_SOLO_ATTR d3 solo_path(KArg karg, int ow, d3 o, d3 d, d3 T, d3 L, 
     clk.solo_lap(5);
     if (!sc.ok) {
       if (dep_out) *dep_out = depth + 1;
-      return L + mul(T, E + D);
+      return path_end(L + mul(T, E + D), T);
     }
     L = L + mul(T, E + muls(D, m->dw));
+    path_step(T, L, sc.A, m->rw);  // (rt_device.h: also before a last bounce, whose black is multiplied too)
     if (!h.recursive || depth + 1 >= h.max_depth) {
       if (dep_out) *dep_out = depth + 1;
-      return L;
+      return path_end(L, T);
     }
-    T = mul(T, muls(sc.A, m->rw));
     o = P;
     d = sc.nd;
     depth += 1;
@@ -2388,6 +2393,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             if constexpr (kSky) {  // an opted-in sky instead of black (rt_settings.sky)
               if (missed) set_path_L(path_L() + mul(T, sky_color(fresh()->sky, d)));
             }
+            if (depth > 0) set_path_L(path_end(path_L(), path_T()));  // (rt_device.h; T = 1 at depth 0)
             if constexpr (kPilot) pilot_record(hl, entry, depth);
             stream_store_row();
             alive = false;  // finished: its radiance is in its slot, the lane is free for the second pass
@@ -2565,13 +2571,17 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           d3 E = ld3(m->emit);
           const Scat sc = scatter<kCount>(m, d, N, front, rng, c);
           if (!sc.ok) {
-            set_path_L(path_L() + mul(path_T(), E + D));
+            const d3 Tp = path_T();
+            set_path_L(path_end(path_L() + mul(Tp, E + D), Tp));
             fin = true;
           } else {
-            set_path_L(path_L() + mul(path_T(), E + muls(D, m->dw)));
+            d3 Tp = path_T();
+            d3 Lp = path_L() + mul(Tp, E + muls(D, m->dw));
+            path_step(Tp, Lp, sc.A, m->rw);  // (rt_device.h: also before a last bounce, whose black is multiplied too)
             fin = !h.recursive || depth + 1 >= h.max_depth;
+            set_path_L(fin ? path_end(Lp, Tp) : Lp);
             if (!fin) {
-              set_path_T(mul(path_T(), muls(sc.A, m->rw)));
+              set_path_T(Tp);
               o = P;
               d = sc.nd;
               depth += 1;

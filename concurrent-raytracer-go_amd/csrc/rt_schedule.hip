@@ -59,10 +59,11 @@ __device__ bool cone_meets_sphere(const double* c, double r, const double* apex,
   const double dc2 = v0 * v0 + v1 * v1 + v2 * v2;
   const double dc = sqrt(dc2);
   const double ra = fabs(r) * (1.0 + 1e-7) + 1e-7 * dc + 1e-12;
-  if (dc <= ra) return true;
+  // ("not provably missed": a NaN centre or radius is kept, as on the host, schedule.cpp)
+  if (!(dc > ra)) return true;
   const double tl = sqrt(fmax(dc2 - ra * ra, 0.0));
   const double vd = v0 * axis[0] + v1 * axis[1] + v2 * axis[2];
-  return vd >= cos_t * (1.0 - 1e-9) * tl - (sin_t + 1e-9) * ra - 1e-7 * dc;
+  return !(vd < cos_t * (1.0 - 1e-9) * tl - (sin_t + 1e-9) * ra - 1e-7 * dc);
 }
 
 // The cone around the camera rays of pixel (x, y): getRay direction

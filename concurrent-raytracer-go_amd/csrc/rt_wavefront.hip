@@ -553,7 +553,19 @@ __global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
           best_obj = -1;
           const d3 id = inv_dir_fast(d);
           cnt<kCount>(c, C_BOX);
-          if (box_hit(p.g.bvh[0], o, id, tmin, closest)) {
+          if (!ray_finite(o, d)) {
+            // no box serves a non-finite ray (rt_device.h ray_finite): every
+            // sphere gets its exact test, and the walk below starts finished
+            HitSelS hs{0, -1};
+            closest_scan<kCount, true>(p.g, o, d, av, inv_a, hs, c);
+            bidx = hs.idx;
+            best_obj = hs.idx >= 0 ? p.g.spheres[hs.idx].obj : -1;
+            closest = hs.num / av;
+            cur = -1;
+            sp = 0;
+            busy = true;
+            miss = false;
+          } else if (box_hit(p.g.bvh[0], o, id, tmin, closest)) {
             r32 = ray_q(p, o, id);
             tminf = t_lo32(tmin);
             cur = bvh_code(p.g.bvh[0]);
@@ -566,7 +578,8 @@ __global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
           // the root box missed: with an opted-in sky, shade1 adds it (kSkyMiss)
           const bool sky = p.sky && sid != kDeadSid && a.depth[slot] < p.max_depth;
           p.hidx[slot] = sky ? kSkyMiss : -1;
-          if (sid != kDeadSid && !sky) finish(p, sid, mk(a.lx[slot], a.ly[slot], a.lz[slot]));
+          if (sid != kDeadSid && !sky)
+            finish(p, sid, path_end(mk(a.lx[slot], a.ly[slot], a.lz[slot]), mk(a.tx[slot], a.ty[slot], a.tz[slot])));
         }
       }
     }
@@ -608,7 +621,7 @@ __global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
           p.hidx[slot] = kSkyMiss;
         } else {
           p.hidx[slot] = -1;
-          finish(p, a.sid[slot], mk(a.lx[slot], a.ly[slot], a.lz[slot]));
+          finish(p, a.sid[slot], path_end(mk(a.lx[slot], a.ly[slot], a.lz[slot]), mk(a.tx[slot], a.ty[slot], a.tz[slot])));
         }
       }
     }
@@ -640,7 +653,7 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade1(const WfParams p) {
     if (hi == kSkyMiss) {  // (opt-in sky) the path ends: L + T * sky(direction)
       const WfPaths& a = p.cur;
       const d3 L = mk(a.lx[slot], a.ly[slot], a.lz[slot]), T = mk(a.tx[slot], a.ty[slot], a.tz[slot]);
-      finish(p, a.sid[slot], L + mul(T, sky_color(p.sky, ld_d(a, slot))));
+      finish(p, a.sid[slot], path_end(L + mul(T, sky_color(p.sky, ld_d(a, slot))), T));
     }
     if (hit) {
       cnt<kCount>(c, C_SHADE);
@@ -749,7 +762,21 @@ __device__ __forceinline__ void occlude_body(const WfParams& p) {
         inv_a = approx_rcp(av);
         const d3 id = inv_dir_fast(d);
         cnt<kCount>(c, C_BOX);
-        if (box_hit(p.g.bvh[0], o, id, tmin, tmax)) {
+        if (!ray_finite(o, d)) {
+          // no box serves a non-finite ray (rt_device.h ray_finite): every sphere gets its exact test
+          bool hit = false;
+          for (int i = 0; i < p.g.ns && !hit; ++i) {
+            cnt<kCount>(c, C_SPH);
+            double num;
+            hit = sphere_query(p.g.spheres[i], o, d, av, inv_a, tmin, tmax, num) != 0;
+          }
+          if (hit) {
+            if constexpr (kSoft)
+              atomicAdd(&p.lstate[key], 1u);
+            else
+              p.lstate[key] = kHardBit;
+          }
+        } else if (box_hit(p.g.bvh[0], o, id, tmin, tmax)) {
           r32 = ray_q(p, o, id);
           tminf = t_lo32(tmin);
           tmaxf = t_hi32(tmax);
@@ -1535,14 +1562,14 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade(const WfParams p) {
         L = L + mul(T, E + D);
       } else {
         L = L + mul(T, E + muls(D, m->dw));
+        path_step(T, L, sc.A, m->rw);  // (rt_device.h: also before a last bounce, whose black is multiplied too)
         cont = p.recursive && depth + 1 < p.max_depth;
         if (cont) {
-          T = mul(T, muls(sc.A, m->rw));
           nd = sc.nd;
           depth += 1;
         }
       }
-      if (!cont) finish(p, sid, L);
+      if (!cont) finish(p, sid, path_end(L, T));
     }
   }
   const int shard = blockIdx.x % kWfShards;

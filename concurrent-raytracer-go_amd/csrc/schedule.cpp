@@ -55,7 +55,9 @@ void tile_cost(const FlatScene& fs, const CamFrame& cf, int32_t W, int32_t H, co
       cz = ox * Wv[0] + oy * Wv[1] + oz * Wv[2];
     }
     if (cz - R >= 0) return;  // entirely behind the camera: no camera ray reaches it
-    if (cz + R > -1e-9 || !(fabs(vw) > 0)) {  // straddles the camera plane: everywhere
+    // straddles the camera plane, or cannot be placed (a non-finite centre or
+    // radius: Sphere.Hit accepts every ray for a NaN one): everywhere
+    if (cz + R > -1e-9 || !(fabs(vw) > 0) || !std::isfinite(cx + cy + cz + R)) {
       for (auto& v : cost) v += 1.0f;
       return;
     }
@@ -71,8 +73,9 @@ void tile_cost(const FlatScene& fs, const CamFrame& cf, int32_t W, int32_t H, co
     }
     const double px0 = u0 * W, px1 = u1 * W, py0 = v0 * H, py1 = v1 * H;
     if (px1 < 0 || py1 < 0 || px0 >= W || py0 >= H) return;
-    const int tx0 = std::max(0, (int)floor(px0) / 32), tx1 = std::min(tiles_x - 1, (int)floor(fmin(px1, W - 1)) / 32);
-    const int ty0 = std::max(0, (int)floor(py0) / 32), ty1 = std::min(tiles_y - 1, (int)floor(fmin(py1, H - 1)) / 32);
+    // (clamped before the conversion: a projection far outside the image does not fit an int)
+    const int tx0 = (int)floor(fmax(px0, 0.0)) / 32, tx1 = std::min(tiles_x - 1, (int)floor(fmin(px1, W - 1)) / 32);
+    const int ty0 = (int)floor(fmax(py0, 0.0)) / 32, ty1 = std::min(tiles_y - 1, (int)floor(fmin(py1, H - 1)) / 32);
     for (int ty = ty0; ty <= ty1; ++ty)
       for (int tx = tx0; tx <= tx1; ++tx) cost[ty * tiles_x + tx] += 1.0f;
   };
@@ -86,16 +89,18 @@ void tile_cost(const FlatScene& fs, const CamFrame& cf, int32_t W, int32_t H, co
 // Does the cone (apex, unit axis, cos/sin of its half-angle) meet the sphere
 // (c, r)?  Same conservative test as the kernel's cone_meets_sphere: radius
 // inflated by ~1e-7, far above binary64 rounding of the ray directions.
+// Written as "not provably missed": a sphere with a NaN centre or radius fails
+// every comparison and is kept (Sphere.Hit accepts every ray for it).
 static bool cone_meets_sphere(const double c[3], double r, const double apex[3], const double axis[3], double cos_t,
                               double sin_t) {
   const double v[3] = {c[0] - apex[0], c[1] - apex[1], c[2] - apex[2]};
   const double dc2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
   const double dc = sqrt(dc2);
   const double ra = fabs(r) * (1.0 + 1e-7) + 1e-7 * dc + 1e-12;
-  if (dc <= ra) return true;
+  if (!(dc > ra)) return true;
   const double tl = sqrt(fmax(dc2 - ra * ra, 0.0));
   const double vd = v[0] * axis[0] + v[1] * axis[1] + v[2] * axis[2];
-  return vd >= cos_t * (1.0 - 1e-9) * tl - (sin_t + 1e-9) * ra - 1e-7 * dc;
+  return !(vd < cos_t * (1.0 - 1e-9) * tl - (sin_t + 1e-9) * ra - 1e-7 * dc);
 }
 
 // The cone around the camera rays of the image rectangle [x0, x1) x [y0, y1)

@@ -337,7 +337,15 @@ void rt_context_destroy(rt_context* ctx);
 
 /* Flatten (GetHittables, scene.go:59-90; createCube, scene.go:150-190) and
  * upload the scene to device memory.  Builds the BVH when the scene is
- * large (or when force_bvh > 0; force_bvh < 0 forbids it). */
+ * large (or when force_bvh > 0; force_bvh < 0 forbids it).  A scene with a
+ * sphere whose centre or radius is not finite never gets a BVH, forced or
+ * not: such a sphere has no bounding box (a NaN one is hit by every ray), and
+ * the linear scan renders it whatever the number of spheres.  Non-finite
+ * geometry is rendered for spheres alone: a cube whose position or size is not
+ * finite, and a sphere whose centre or radius is not finite in a scene that
+ * has a cube, are refused with RT_E_INVALID (by every entry point that takes
+ * a scene, rt_validate included); the message names the object and the field.
+ * Non-finite lights and materials are accepted. */
 int rt_context_set_scene(rt_context* ctx, const rt_scene* scene, int32_t force_bvh);
 
 /* Work-partition tuning.  No setting changes a single output bit (the GPU

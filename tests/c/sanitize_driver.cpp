@@ -10,7 +10,10 @@
 // bin settings) and the schedule's per-tile inputs; truncated and ill-typed
 // JSON; the PNG / PPM writers and the tone map; and small multi-threaded
 // oracle renders (the tile queue of renderer.go:67-148).
+// The degenerate scenes (tests/golden/degenerate_scenes.txt, found from the
+// scenes dir) go through the same host paths and the oracle.
 //   usage: sanitize_driver <scenes dir> <10k scene json> <tmp dir>
+//          sanitize_driver --degenerate <degenerate_scenes.txt>
 #include <dirent.h>
 #include <math.h>
 #include <stdio.h>
@@ -67,19 +70,145 @@ static void exercise_scene(const rt_scene* s, const char* name) {
         CHECK(pd.owner[pd.lists[k]] == r && pd.local[pd.lists[k]] == k - pd.offsets[r]);
   }
   if (f.tris.empty() && !f.spheres.empty()) {
+    // (a scene with a non-finite sphere gets no BVH: it keeps the linear scan)
+    bool finite = true;
+    for (const DSphere& sp : f.spheres) finite = finite && isfinite(sp.c[0] + sp.c[1] + sp.c[2] + sp.r);
     for (int leaf : {0, 1, 7})
-      for (int bins : {0, 2, 64}) {
+      for (int bins : {0, 2, 4, 64}) {
         FlatScene g = f;
         build_sphere_bvh(&g, bins, leaf);
-        CHECK(!g.bvh.empty() && g.qbvh.size() == g.bvh.size());
+        CHECK(g.bvh.empty() == !finite && g.qbvh.size() == g.bvh.size());
       }
   }
   printf("%s: %zu spheres, %zu triangles, %zu lights\n", name, f.spheres.size(), f.tris.size(), f.lights.size());
 }
 
+// The degenerate scenes of tests/degenerate_cases.py (negative and zero radii,
+// coincident primitives, flat cubes, non-finite lights, materials and
+// geometry), read from tests/golden/degenerate_scenes.txt: one record per
+// line, numbers as strtod reads them ("nan", "inf" included).  Each goes
+// through exercise_scene, the tile inputs at the GPU tests' 72x48, once more
+// without its cubes (the BVH builder is for sphere-only scenes) and a small
+// multi-threaded oracle render.
+static bool read_doubles(char** p, double* out, int n) {
+  for (int i = 0; i < n; ++i) {
+    char* e = nullptr;
+    out[i] = strtod(*p, &e);
+    if (e == *p) return false;
+    *p = e;
+  }
+  return true;
+}
+
+static void exercise_degenerate(const rt_scene& s, const std::string& name) {
+  exercise_scene(&s, name.c_str());
+  FlatScene f;
+  flatten_scene(s, &f);
+  std::vector<int32_t> tiles;
+  std::vector<unsigned long long> masks;
+  std::vector<float> cost;
+  strided_tiles(72, 48, 0, 1, &tiles);
+  if (f.spheres.size() <= 64 && f.tris.size() <= 64) {
+    tile_primary_masks(f, 72, 48, tiles, &masks);
+    CHECK(masks.size() == 2 * tiles.size());
+  }
+  tile_cost(f, 72, 48, tiles, &cost);
+  CHECK(cost.size() == tiles.size());
+  for (float c : cost) CHECK(c >= 0.0f && c <= (float)(f.spheres.size() + f.tris.size()));
+  if (!f.tris.empty()) {  // the same spheres without the cubes
+    std::vector<rt_object> so;
+    for (int i = 0; i < s.num_objects; ++i)
+      if (s.objects[i].type == RT_OBJ_SPHERE) so.push_back(s.objects[i]);
+    rt_scene t = s;
+    t.objects = so.data();
+    t.num_objects = (int32_t)so.size();
+    exercise_scene(&t, (name + " (spheres)").c_str());
+  }
+  rt_settings st;
+  rt_settings_default(&st);
+  st.samples = 2;
+  st.max_depth = 8;
+  std::vector<double> out((size_t)24 * 16 * 3);
+  std::vector<uint8_t> o8((size_t)24 * 16 * 4);
+  rt_counts c;
+  CHECK(oracle_render(&s, 24, 16, &st, 0, 1, 3, -1, out.data(), o8.data(), &c) == 0);
+}
+
+static void degenerate_scenes(const std::string& path) {
+  FILE* fp = fopen(path.c_str(), "r");
+  CHECK(fp != nullptr);
+  if (!fp) return;
+  std::vector<char> line(4096);
+  std::string name;
+  rt_scene s;
+  std::vector<rt_object> objs;
+  std::vector<rt_light> lights;
+  int scenes = 0;
+  while (fgets(line.data(), (int)line.size(), fp)) {
+    char* p = line.data();
+    if (!strncmp(p, "scene ", 6)) {
+      name = std::string(p + 6);
+      while (!name.empty() && (name.back() == '\n' || name.back() == '\r')) name.pop_back();
+      memset(&s, 0, sizeof s);
+      objs.clear();
+      lights.clear();
+    } else if (!strncmp(p, "camera ", 7)) {
+      p += 7;
+      double v[11];
+      CHECK(read_doubles(&p, v, 11));
+      memcpy(s.camera.position, v, sizeof(double) * 3);
+      memcpy(s.camera.look_at, v + 3, sizeof(double) * 3);
+      memcpy(s.camera.up, v + 6, sizeof(double) * 3);
+      s.camera.fov = v[9];
+      s.camera.aspect_ratio = v[10];
+    } else if (!strncmp(p, "object ", 7)) {
+      p += 7;
+      rt_object o;
+      memset(&o, 0, sizeof o);
+      double t, v[7], k, m[7];
+      CHECK(read_doubles(&p, &t, 1) && read_doubles(&p, v, 7) && read_doubles(&p, &k, 1) && read_doubles(&p, m, 7));
+      o.type = (int32_t)t;
+      memcpy(o.position, v, sizeof(double) * 3);
+      memcpy(o.size, v + 3, sizeof(double) * 3);
+      o.radius = v[6];
+      o.material.kind = (int32_t)k;
+      memcpy(o.material.color, m, sizeof(double) * 3);
+      o.material.roughness = m[3];
+      o.material.metallic = m[4];
+      o.material.specular = m[5];
+      o.material.refraction_index = m[6];
+      objs.push_back(o);
+    } else if (!strncmp(p, "light ", 6)) {
+      p += 6;
+      rt_light l;
+      double v[7];
+      CHECK(read_doubles(&p, v, 7));
+      memcpy(l.position, v, sizeof(double) * 3);
+      memcpy(l.color, v + 3, sizeof(double) * 3);
+      l.intensity = v[6];
+      lights.push_back(l);
+    } else if (!strncmp(p, "end", 3)) {
+      s.objects = objs.data();
+      s.num_objects = (int32_t)objs.size();
+      s.lights = lights.data();
+      s.num_lights = (int32_t)lights.size();
+      exercise_degenerate(s, name);
+      ++scenes;
+    }
+  }
+  fclose(fp);
+  CHECK(scenes >= 20);
+}
+
 int main(int argc, char** argv) {
+  if (argc == 3 && !strcmp(argv[1], "--degenerate")) {  // the degenerate scenes alone
+    degenerate_scenes(argv[2]);
+    printf("sanitize_driver: %d failures\n", failures);
+    return failures ? 1 : 0;
+  }
   if (argc < 4) return 2;
   const std::string dir = argv[1], big = argv[2], tmp = argv[3];
+  degenerate_scenes(dir + "/../tests/golden/degenerate_scenes.txt");
   // every committed scene
   DIR* d = opendir(dir.c_str());
   CHECK(d != nullptr);
