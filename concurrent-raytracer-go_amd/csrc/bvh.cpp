@@ -1,4 +1,4 @@
-// bvh.cpp — binned-SAH bounding volume hierarchy over spheres.
+// bvh.cpp — binned-SAH bounding volume hierarchy over spheres and cubes.
 //
 // The reference's live path has no acceleration structure: hitWorld is a
 // linear closest-hit scan (internal/renderer/renderer.go:333-346), and its
@@ -16,6 +16,15 @@
 // test runs in binary32 on the ray origin rounded to float, an error of at
 // most 2^-24 * M per axis, which the padding covers 64 times over.
 // Spheres are reordered so every leaf is a contiguous range.
+//
+// A cube is one primitive, its DBox (the padded box of its 12 triangles,
+// scene_flat.cpp), padded once more like a sphere's box.  Leaves hold one
+// kind: a sphere leaf is first << 3 | count into the reordered sphere array,
+// a cube leaf carries kCubeLeafBit in `first` and indexes the DBox array,
+// which is reordered the same way (the triangles stay: DBox.first finds
+// them).  A node that SAH would close as a leaf while it still holds both
+// kinds is split by kind instead, one level more.  Without cubes the tree is
+// the sphere tree, node for node.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -83,7 +92,21 @@ bool spheres_finite(const FlatScene& fs) {
   return true;
 }
 
-void build_sphere_bvh(FlatScene* fs, int bins, int leaf) {
+// Every cube's box is finite (validate_scene refuses the others; the builder
+// does not rely on it).
+static bool boxes_finite(const FlatScene& fs) {
+  for (const DBox& b : fs.boxes)
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(b.lo[k] + b.hi[k])) return false;
+  return true;
+}
+
+void build_sphere_bvh(FlatScene* fs, int bins, int leaf) { build_bvh(fs, bins, leaf); }
+
+// (every cube of a scene with a tree is in one of its leaves)
+bool bvh_has_cubes(const FlatScene& fs) { return !fs.bvh.empty() && !fs.boxes.empty(); }
+
+void build_bvh(FlatScene* fs, int bins, int leaf) {
   // rt_tuning: bins, leaf (<= 7: a 3-bit count); 0 = the defaults
   const int kBins = bins > 0 ? std::max(2, std::min(kMaxBins, bins)) : kDefaultBins;
   const int kLeafMax = leaf > 0 ? std::min(7, leaf) : kDefaultLeaf;
@@ -92,16 +115,28 @@ void build_sphere_bvh(FlatScene* fs, int bins, int leaf) {
   fs->qbvh4.clear();
   fs->bvh4_stack = 0;
   fs->bvh4_root = 0;
-  const int n = (int)fs->spheres.size();
-  if (n == 0 || !spheres_finite(*fs)) return;  // (no BVH: the scene keeps the linear scan)
+  // primitives: the spheres, then the cubes
+  const int ns = (int)fs->spheres.size(), n = ns + (int)fs->boxes.size();
+  if (n == 0 || n >= kCubeLeafBit || !spheres_finite(*fs) || !boxes_finite(*fs))
+    return;  // (no BVH: the scene keeps the linear scan)
   std::vector<Box> pb(n);
   std::vector<double> cen(3 * (size_t)n);
   double M = 1.0;
   for (int k = 0; k < 3; ++k) M = std::max(M, fabs(fs->cam_pos[k]));
-  for (int i = 0; i < n; ++i)
+  for (int i = 0; i < ns; ++i)
     for (int k = 0; k < 3; ++k) M = std::max(M, fabs(fs->spheres[i].c[k]) + fabs(fs->spheres[i].r));
+  for (const DBox& b : fs->boxes)
+    for (int k = 0; k < 3; ++k) M = std::max(M, std::max(fabs(b.lo[k]), fabs(b.hi[k])));
   const double pad = ldexp(M, -18);
-  for (int i = 0; i < n; ++i) {
+  for (int i = ns; i < n; ++i) {
+    const DBox& b = fs->boxes[i - ns];
+    for (int k = 0; k < 3; ++k) {
+      pb[i].lo[k] = b.lo[k] - pad;
+      pb[i].hi[k] = b.hi[k] + pad;
+      cen[3 * (size_t)i + k] = b.bc[k];
+    }
+  }
+  for (int i = 0; i < ns; ++i) {
     const DSphere& s = fs->spheres[i];
     double r = fabs(s.r);
     for (int k = 0; k < 3; ++k) {
@@ -136,12 +171,30 @@ void build_sphere_bvh(FlatScene* fs, int bins, int leaf) {
       nd.lo[k] = down(b.lo[k]);
       nd.hi[k] = up(b.hi[k]);
     }
+    // (a leaf's `first` is its position in idx until the tree is complete)
     auto make_leaf = [&]() {
       nodes[t.node].left_or_first = t.first;
       nodes[t.node].count = t.count;
     };
-    if (t.count <= kLeafMax) {
+    int cubes = 0;
+    for (int i = t.first; i < t.first + t.count; ++i) cubes += idx[i] >= ns;
+    if (cubes == 0 ? t.count <= kLeafMax : (cubes == t.count && t.count <= kBvhCubeLeaf)) {
       make_leaf();
+      continue;
+    }
+    if (cubes != 0 && cubes != t.count && t.count <= kLeafMax) {
+      // SAH would close this node as a leaf, but it holds both kinds: the
+      // spheres go left (a leaf), the cubes right (a leaf, or split further)
+      auto it = std::stable_partition(idx.begin() + t.first, idx.begin() + t.first + t.count,
+                                      [&](int i) { return i < ns; });
+      const int mid = (int)(it - idx.begin());
+      const int left = (int)nodes.size();
+      nodes.push_back(DBVHNode{});
+      nodes.push_back(DBVHNode{});
+      nodes[t.node].left_or_first = left;
+      nodes[t.node].count = 0;
+      stack.push_back({left + 1, mid, t.first + t.count - mid});
+      stack.push_back({left, t.first, mid - t.first});
       continue;
     }
     // binned SAH along each axis
@@ -211,6 +264,15 @@ void build_sphere_bvh(FlatScene* fs, int bins, int leaf) {
     nodes[t.node].count = 0;
     stack.push_back({left + 1, mid, t.first + t.count - mid});
     stack.push_back({left, t.first, mid - t.first});
+  }
+  // leaves: from positions in idx to positions in the reordered sphere / DBox
+  // arrays (every leaf holds one kind; without cubes the two are the same)
+  {
+    std::vector<int> rank(n);
+    int s = 0, b = 0;
+    for (int i = 0; i < n; ++i) rank[i] = idx[i] < ns ? s++ : (b++ | kCubeLeafBit);
+    for (DBVHNode& nd : nodes)
+      if (nd.count != 0) nd.left_or_first = rank[nd.left_or_first];
   }
   // breadth-first renumbering (child pairs stay adjacent): the top levels of
   // the tree become a prefix of the node array, which the wavefront traversal
@@ -346,9 +408,18 @@ void build_sphere_bvh(FlatScene* fs, int bins, int leaf) {
       fs->bvh4_root = (int32_t)code(0);
     }
   }
-  std::vector<DSphere> reordered(n);
-  for (int i = 0; i < n; ++i) reordered[i] = fs->spheres[idx[i]];
+  std::vector<DSphere> reordered;
+  std::vector<DBox> reboxed;
+  reordered.reserve(ns);
+  reboxed.reserve(n - ns);
+  for (int i = 0; i < n; ++i) {
+    if (idx[i] < ns)
+      reordered.push_back(fs->spheres[idx[i]]);
+    else
+      reboxed.push_back(fs->boxes[idx[i] - ns]);
+  }
   fs->spheres.swap(reordered);
+  fs->boxes.swap(reboxed);
   fs->bvh.swap(nodes);
 }
 

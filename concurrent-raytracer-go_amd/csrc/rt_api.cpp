@@ -381,16 +381,14 @@ int rt_context_set_scene(rt_context* c, const rt_scene* s, int32_t force_bvh) {
   flatten_scene(*s, &c->flat);
   c->bvh_seconds = 0;
   // (a sphere with a non-finite centre or radius: no BVH, even when forced; rt_api.h)
+  // (a cube is one primitive of the tree, bvh.cpp; kAutoBvhCubes: rt_api.h)
   const bool want_bvh =
-      (force_bvh > 0 || (force_bvh == 0 && c->flat.spheres.size() > 64)) && spheres_finite(c->flat);
-  if (want_bvh && !c->flat.tris.empty()) {
-    if (force_bvh > 0) {
-      set_error("BVH supports sphere-only scenes");
-      return RT_E_INVALID;
-    }
-  } else if (want_bvh) {
+      (force_bvh > 0 ||
+       (force_bvh == 0 && (c->flat.spheres.size() > 64 || c->flat.boxes.size() > (size_t)kAutoBvhCubes))) &&
+      spheres_finite(c->flat);
+  if (want_bvh) {
     const auto t0 = std::chrono::steady_clock::now();
-    build_sphere_bvh(&c->flat, c->tun.bvh_bins, c->tun.bvh_leaf);
+    build_bvh(&c->flat, c->tun.bvh_bins, c->tun.bvh_leaf);
     c->bvh_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
   const FlatScene& f = c->flat;

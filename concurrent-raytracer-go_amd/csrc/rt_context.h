@@ -268,7 +268,7 @@ inline void base_params(const rt_context* c, int w, int h, const rt_settings* st
   p.nt = (int32_t)f.tris.size();
   p.nl = (int32_t)f.lights.size();
   p.nb = (int32_t)f.boxes.size();
-  p.use_bvh = f.bvh.empty() ? 0 : 1;
+  p.use_bvh = f.bvh.empty() ? 0 : (bvh_has_cubes(f) ? 2 : 1);  // (2: leaves of cubes, launch_render's kMix kernels)
   p.W = w;
   p.H = h;
   p.spp = st->samples;

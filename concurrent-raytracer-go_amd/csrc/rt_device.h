@@ -301,7 +301,8 @@ __device__ __forceinline__ bool box_hit32(const DBVHNode& n, const Ray32& r, flo
 }
 // BVH traversal state: a node is (first << 3) | count, count 0 = internal
 // node whose children are the adjacent records first, first + 1 (bvh.cpp),
-// count 1..4 = leaf of spheres [first, first + count).  Children are tested
+// count 1..7 = leaf of spheres [first, first + count), or with kCubeCode set a
+// leaf of cubes (DBox) [first, first + count).  Children are tested
 // together, from the one 64-B load of their two records; the nearer one hit
 // is entered and the other pushed, so the per-lane LDS stack holds ready
 // node codes and a pop needs no memory access.
@@ -433,7 +434,7 @@ __device__ __forceinline__ bool ray_finite(d3 o, d3 d) {
 // such a ray is not nearer than the closest so far (t is NaN), so the scan
 // ends with the last accepted hittable: here, the largest hittable index
 // among the hits that are not strictly nearer.
-template <bool kCount, bool kSph>
+template <bool kCount, bool kSph, bool kMix = false>
 __device__ __forceinline__ bool closest_scan(const Geo& p, d3 o, d3 d, double a, double inv_a,
                                              typename Kind<kSph>::H& hs, Counters& c) {
   double closest = __builtin_inf();
@@ -452,13 +453,86 @@ __device__ __forceinline__ bool closest_scan(const Geo& p, d3 o, d3 d, double a,
       best_obj = S.obj;
     }
   }
+  if constexpr (kMix) {
+    // the cubes of a mixed tree, in the DBox array's (BVH) order, by the same
+    // rule: Triangle.Hit (triangle.go:36-66) of such a ray gives t = NaN or
+    // +Inf where it accepts at all, never a nearer hit
+    const d3 id = inv_dir(d);
+    for (int j = 0; j < p.nb; ++j) {
+      const DBox& B = p.boxes[j];
+      if (!ray_box(B, o, id, 0.001, closest)) continue;
+      for (int i = B.first; i < B.first + B.count; ++i) {
+        cnt<kCount>(c, C_TRI);
+        const DTri& T = p.tris[i];
+        double t, u, v;
+        if (tri_test(T, o, d, 0.001, closest, t, u, v)) {
+          if (!(t < closest) && best_obj > T.obj) continue;
+          closest = t;
+          hs.num = t;
+          hs.u = u;
+          hs.v = v;
+          hs.idx = i;
+          hs.is_tri = 1;
+          best_obj = T.obj;
+        }
+      }
+    }
+  }
   return best_obj >= 0;
+}
+
+// The cubes of a BVH leaf (bvh.cpp: kCubeCode in the leaf's code, `first`
+// indexes the DBox array): the linear scan's per-cube loop of closest_hit,
+// so an exact-t tie resolves by hittable index whatever order the leaves are
+// visited in.
+template <bool kCount>
+__device__ __forceinline__ void closest_cube_leaf(const Geo& p, int cur, d3 o, d3 d, d3 id, double tmin,
+                                                  double& closest, int& best_obj, bool& found, HitSel& hs,
+                                                  Counters& c) {
+  const int first = (cur & ~kCubeCode) >> 3, count = cur & 7;
+  for (int j = first; j < first + count; ++j) {
+    const DBox& B = p.boxes[j];
+    if (!ray_box(B, o, id, tmin, closest)) continue;
+    for (int i = B.first; i < B.first + B.count; ++i) {
+      cnt<kCount>(c, C_TRI);
+      const DTri& T = p.tris[i];
+      double t, u, v;
+      if (tri_test(T, o, d, tmin, closest, t, u, v)) {
+        if (t == closest && best_obj > T.obj) continue;
+        closest = t;
+        hs.num = t;
+        hs.u = u;
+        hs.v = v;
+        hs.idx = i;
+        hs.is_tri = 1;
+        best_obj = T.obj;
+        found = true;
+      }
+    }
+  }
+}
+// ... and as an occlusion query
+template <bool kCount>
+__device__ __forceinline__ bool any_cube_leaf(const Geo& p, int cur, d3 o, d3 d, d3 id, double tmin, double tmax,
+                                              Counters& c) {
+  const int first = (cur & ~kCubeCode) >> 3, count = cur & 7;
+  for (int j = first; j < first + count; ++j) {
+    const DBox& B = p.boxes[j];
+    if (!ray_box(B, o, id, tmin, tmax)) continue;
+    for (int i = B.first; i < B.first + B.count; ++i) {
+      cnt<kCount>(c, C_TRI);
+      double t, u, v;
+      if (tri_test(p.tris[i], o, d, tmin, tmax, t, u, v)) return true;
+    }
+  }
+  return false;
 }
 
 // hitWorld closest hit, renderer.go:333-346.  Linear scan in hittable order
 // (spheres before triangles; an exact-t tie is resolved by hittable index so
 // the later hittable wins, as in Go), or BVH traversal with the same rule.
-template <bool kCount, bool kSph = false>
+// (kMix: the tree has leaves of cubes, bvh.cpp; never with kSph)
+template <bool kCount, bool kSph = false, bool kMix = false>
 __device__ __forceinline__ bool closest_hit(const Geo& p, d3 o, d3 d, typename Kind<kSph>::H& hs, int* stack,
                                             typename Kind<kSph>::C m, Counters& c) {
   const double tmin = 0.001;
@@ -467,7 +541,7 @@ __device__ __forceinline__ bool closest_hit(const Geo& p, d3 o, d3 d, typename K
   int best_obj = -1;
   const double a = len2(d);
   const double inv_a = approx_rcp(a);
-  if (p.use_bvh && !ray_finite(o, d)) return closest_scan<kCount, kSph>(p, o, d, a, inv_a, hs, c);
+  if (p.use_bvh && !ray_finite(o, d)) return closest_scan<kCount, kSph, kMix>(p, o, d, a, inv_a, hs, c);
   if (p.use_bvh) {
     const d3 id = inv_dir(d);
     int sp = 0;
@@ -499,6 +573,13 @@ __device__ __forceinline__ bool closest_hit(const Geo& p, d3 o, d3 d, typename K
         }
       }
       if (cur == -1) break;
+      if constexpr (kMix) {
+        if (cur & kCubeCode) {
+          closest_cube_leaf<kCount>(p, cur, o, d, id, tmin, closest, best_obj, found, hs, c);
+          cur = sp == 0 ? -1 : stack[--sp * 64];
+          continue;
+        }
+      }
       const int first = cur >> 3, count = cur & 7;
       for (int i = first; i < first + count; ++i) {
         cnt<kCount>(c, C_SPH);
@@ -571,7 +652,7 @@ __device__ __forceinline__ bool closest_hit(const Geo& p, d3 o, d3 d, typename K
 // hitWorld used as an occlusion query over everything (BVH or large linear
 // scenes): calculateSmartShadow only asks whether any hittable is hit in
 // [tmin, tmax] (renderer.go:305,320).
-template <bool kCount>
+template <bool kCount, bool kSph = false, bool kMix = false>
 __device__ __forceinline__ bool any_hit(const Geo& p, d3 o, d3 d, double tmax, int* stack, Counters& c) {
   const double tmin = 0.001;
   const double a = len2(d);
@@ -605,6 +686,13 @@ __device__ __forceinline__ bool any_hit(const Geo& p, d3 o, d3 d, double tmax, i
         }
       }
       if (cur == -1) break;
+      if constexpr (kMix) {
+        if (cur & kCubeCode) {
+          if (any_cube_leaf<kCount>(p, cur, o, d, id, tmin, tmax, c)) return true;
+          cur = sp == 0 ? -1 : stack[--sp * 64];
+          continue;
+        }
+      }
       const int first = cur >> 3, count = cur & 7;
       for (int i = first; i < first + count; ++i) {
         cnt<kCount>(c, C_SPH);

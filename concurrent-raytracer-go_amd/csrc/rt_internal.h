@@ -71,10 +71,17 @@ void sky_presets(DSky out[kSkies]);
 
 // GetHittables + createCube + material constructors (scene.go:59-190).
 void flatten_scene(const rt_scene& s, FlatScene* out);
-// Binned-SAH BVH over out->spheres (reorders spheres). Requires no triangles.
-// bins / leaf: SAH bins per axis and spheres per leaf at most (0: defaults).
+// Binned-SAH BVH over out->spheres and out->boxes, a cube being one primitive
+// (reorders both arrays; the triangles stay).  Leaves hold one kind.
+// bins / leaf: SAH bins per axis and spheres per leaf at most (0: defaults);
+// cubes per leaf is a constant of bvh.cpp.
 // Leaves fs->bvh empty (the linear scan) when !spheres_finite(*fs).
+void build_bvh(FlatScene* fs, int bins, int leaf);
+// The same (its name from when the tree held spheres alone): without cubes
+// the tree is node for node what it always was.
 void build_sphere_bvh(FlatScene* fs, int bins, int leaf);
+// The tree has a leaf of cubes.
+bool bvh_has_cubes(const FlatScene& fs);
 // Every sphere's centre and radius is finite (a BVH can hold it).
 bool spheres_finite(const FlatScene& fs);
 // The global tiles a rank renders, in local-tile order (local tile lt is
@@ -174,6 +181,21 @@ constexpr int kGroupSoft = 2, kGroupExtend = 3, kGroupHard = 4;
 // the linear scan for deeper trees).  The stacks are allocated per launch for
 // the scene's actual depth (10k spheres: 15 levels).
 constexpr int kStack = 40;
+// A leaf of cubes (bvh.cpp): this bit of DBVHNode.left_or_first, the rest of
+// it the first DBox of the leaf; kCubeCode is the same bit in a traversal
+// code (first << 3 | count).  Sphere leaves and internal nodes never set it.
+constexpr int kCubeLeafBit = 1 << 27;
+constexpr int kCubeCode = kCubeLeafBit << 3;
+// Cubes per leaf at most: each is a box test and up to 12 triangle tests
+// (rt_tuning.bvh_leaf stays the spheres per leaf).
+constexpr int kBvhCubeLeaf = 2;
+// rt_context_set_scene, force_bvh == 0: a scene of at most 64 spheres gets a
+// tree once it has more cubes than this.  Cubes-only grids at 640x480x16,
+// linear scan / tree on the wavefront path (scripts/mixed_bvh_ab.py sweep,
+// profiles/mixed_bvh_ab.txt): 8 cubes 5.1 / 19.4 ms, 16: 14.3 / 19.7, 32: 9.9 /
+// 20.1, 64: 17.3 / 20.5, 128: 31.8 / 21.0 -- 64 is the largest count at which
+// the scan still wins.
+constexpr int kAutoBvhCubes = 64;
 
 // ---- tail helpers: a launch's long paths handed to idle waves
 // When a block's wave has started every entry of its hit list and only a
@@ -466,7 +488,7 @@ struct WfParams {
   uint64_t seed_key;
   WfPaths cur, next;
   WfCtl* ctl;
-  int32_t* hidx;             // per slot of the current array: sphere hit (-1: none)
+  int32_t* hidx;             // per slot of the current array: sphere hit (-1: none; kTriHit | triangle, rt_wavefront.hip)
   double *px, *py, *pz;      // hit point
   uint32_t* lstate;          // [slot][light]: kHardBit | blocked soft rays
   uint32_t* hardq;           // kWfShards queues of hard_cap entries: slot * nl + light

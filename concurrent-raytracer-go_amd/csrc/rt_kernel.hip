@@ -230,11 +230,11 @@ __device__ __forceinline__ bool any_hit_masked(const Geo& p, d3 o, d3 d, double 
 
 // Occlusion of one shadow ray: candidates when culling is on, else all.
 // (kSph: any_hit's triangle loops fold away, hot() sets nt = nb = 0)
-template <bool kCount, bool kSph = false>
+template <bool kCount, bool kSph = false, bool kMix = false>
 __device__ __forceinline__ bool shadow_blocked(const Geo& p, bool masks, d3 o, d3 d, double tmax,
                                                typename Kind<kSph>::C m, int* stack, Counters& c) {
   if (masks) return cand_any(m) && any_hit_masked<kCount, kSph>(p, o, d, tmax, m, c);
-  return any_hit<kCount>(p, o, d, tmax, stack, c);
+  return any_hit<kCount, kSph, kMix>(p, o, d, tmax, stack, c);
 }
 
 // ------------------------------------------------------------ wide mode
@@ -381,7 +381,7 @@ struct CoopOut {
 // the candidates of lane `ow`, wave-uniform
 __device__ __forceinline__ Cand cand_of_lane(Cand m, int ow) { return Cand{rl64(m.s, ow), rl64(m.t, ow)}; }
 __device__ __forceinline__ CandS cand_of_lane(CandS m, int ow) { return CandS{rl64(m.s, ow)}; }
-template <bool kCount, bool kSph = false>
+template <bool kCount, bool kSph = false, bool kMix = false>
 __device__ __forceinline__ CoopOut soft_coop(const Geo p, bool masks, bool trace, d3 P, d3 ldir, double ldist,
                              typename Kind<kSph>::C cm, uint64_t x, const uint64_t* jump, int* stack, Counters& c) {
   const int lane = (int)(threadIdx.x & 63);
@@ -400,7 +400,7 @@ __device__ __forceinline__ CoopOut soft_coop(const Geo p, bool masks, bool trace
     const int used = nch == need ? 64 - __clzll(chm) : 64;
     bool occ = false;
     if (chosen && trace)
-      occ = shadow_blocked<kCount, kSph>(p, masks, P, normalize(ldir + muls(unit_ball_point(o0, o1, o2), 0.1)), ldist,
+      occ = shadow_blocked<kCount, kSph, kMix>(p, masks, P, normalize(ldir + muls(unit_ball_point(o0, o1, o2), 0.1)), ldist,
                                          cm, stack, c);
     unocc += nch - __popcll(__ballot(chosen && occ));
     need -= nch;
@@ -422,7 +422,7 @@ __device__ __forceinline__ CoopOut soft_coop(const Geo p, bool masks, bool trace
 // lanes; here the tries run alone and the rays run on full waves.  The
 // result is a count of unoccluded rays, so the order in which rays are
 // traced does not change it.  Returns the owner's count (0 elsewhere).
-template <bool kCount, bool kSph = false>
+template <bool kCount, bool kSph = false, bool kMix = false>
 __device__ __forceinline__ int soft_queue(const Geo& p, bool masks, bool need_soft, bool trace, d3 P, d3 ldir,
                                           double ldist, typename Kind<kSph>::C cm, rt_rng& rng, const uint64_t* jump,
                                           int* stack, Counters& c) {
@@ -535,7 +535,7 @@ __device__ __forceinline__ int soft_queue(const Geo& p, bool masks, bool need_so
       if constexpr (!kSph) co.t = p.nt ? __shfl(cm.t, ow) : 0ull;  // (no triangles: cm.t is 0)
       if (lane < n) {
         const d3 pt = mk(rt_bits_to_unit(e.x) * 2 - 1, rt_bits_to_unit(e.y) * 2 - 1, rt_bits_to_unit(e.z) * 2 - 1);
-        if (!shadow_blocked<kCount, kSph>(p, masks, Po, normalize(Lo + muls(pt, 0.1)), dist, co, stack, c))
+        if (!shadow_blocked<kCount, kSph, kMix>(p, masks, Po, normalize(Lo + muls(pt, 0.1)), dist, co, stack, c))
           atomicAdd(&sq_unocc[ow], 1);
       }
       head += n;
@@ -1883,10 +1883,15 @@ struct BodySwitches {  // (the defaults: a variant names only what it turns on)
   static constexpr bool stream = false;  // drains the launch-wide entry queue
   static constexpr bool base = false;    // (stream) entry samples start at sample_base
   static constexpr bool sph = false;     // (stream) the scene is spheres alone
+  static constexpr bool mix = false;     // the BVH has leaves of cubes (bvh.cpp; KParams.use_bvh == 2)
 };
 template <bool kCount, bool kStage, bool kPilot, bool kSky>
 struct BlockBody : BodySwitches {  // render_kernel<kCount, kStage, kPilot, kSky>
   static constexpr bool count = kCount, stage = kStage, pilot = kPilot, sky = kSky;
+};
+template <bool kCount, bool kPilot, bool kSky>
+struct MixBody : BlockBody<kCount, false, kPilot, kSky> {  // render_kernel_mix<kCount, kPilot, kSky>
+  static constexpr bool mix = true;
 };
 struct TailBody : BodySwitches {  // render_kernel_tail
   static constexpr bool stage = true, tail = true;
@@ -1907,6 +1912,7 @@ template <class V>
 constexpr bool body_variant_ok() {
   static_assert(!V::stream || (V::stage && !V::count && !V::pilot && !V::sky && !V::tail), "the stream kernel is the staged product body");
   static_assert(!V::sph || V::stream, "spheres-only is a build of the stream kernel");
+  static_assert(!V::mix || (!V::stage && !V::stream && !V::tail), "a BVH scene is not staged");
   return true;
 }
 
@@ -1914,7 +1920,7 @@ template <class V>
 __device__ __forceinline__ void render_body(const KParams& pk) {
   static_assert(body_variant_ok<V>(), "");
   constexpr bool kCount = V::count, kStage = V::stage, kPilot = V::pilot, kSky = V::sky, kStream = V::stream,
-                 kBase = V::base, kSph = V::sph;
+                 kBase = V::base, kSph = V::sph, kMix = V::mix;
   typedef typename Kind<kSph>::C CandK;
   typedef typename Kind<kSph>::H HitK;
   __shared__ uint32_t hbits[kStream ? 1 : kMaxBlockSamples / 32];  // hit samples of the block
@@ -2056,7 +2062,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
         // hit or miss is all this phase needs: an any-hit query over
         // [0.001, +inf) decides exactly what hitWorld's closest hit would
         const bool hit = sky || (h.masks ? any_hit_masked<kCount>(h.g, o, d, __builtin_inf(), prim, cs)
-                                         : any_hit<kCount>(h.g, o, d, __builtin_inf(), stack, cs));
+                                         : any_hit<kCount, false, kMix>(h.g, o, d, __builtin_inf(), stack, cs));
         if (hit) atomicOr(&hbits[id >> 5], 1u << (id & 31));
       }();
       if constexpr (kCount) {
@@ -2381,11 +2387,11 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           if (!done) {
             if (kCount && depth == 0) {  // phase 1 counted the primary query
               Counters nc;
-              done = (wide_q && !wide_fb) ? !wide_found : !closest_hit<false, kSph>(gg, o, d, hs, stack, all, nc);
+              done = (wide_q && !wide_fb) ? !wide_found : !closest_hit<false, kSph, kMix>(gg, o, d, hs, stack, all, nc);
             } else {
               cnt<kCount>(c, C_BOUNCE);
               done = (wide_q && !wide_fb) ? !wide_found
-                                          : !closest_hit<kCount, kSph>(gg, o, d, hs, stack, all, c);  // miss -> black
+                                          : !closest_hit<kCount, kSph, kMix>(gg, o, d, hs, stack, all, c);  // miss -> black
             }
             missed = done;
           }
@@ -2481,14 +2487,14 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             if (masks && !wide_c) cm = cone_candidates<kSph>(gg, P, N, front, self, ldir, ldist);
             if constexpr (kCount) {
               const unsigned long long s0 = c.v[C_SPH], t0 = c.v[C_TRI];
-              occl = shadow_blocked<kCount, kSph>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray
+              occl = shadow_blocked<kCount, kSph, kMix>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray
               if (dark) {
                 culled.v[C_SHADOW] += 1;
                 culled.v[C_SPH] += c.v[C_SPH] - s0;
                 culled.v[C_TRI] += c.v[C_TRI] - t0;
               }
             } else {
-              occl = shadow_blocked<kCount, kSph>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray
+              occl = shadow_blocked<kCount, kSph, kMix>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray
             }
           }
           clk.end(kClkHard);
@@ -2530,7 +2536,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             if (__popcll(owners) <= kCoopMax) {
               for (unsigned long long b = owners; b; b &= b - 1) {
                 const int ow = __builtin_ctzll(b);
-                const CoopOut r = soft_coop<kCount, kSph>(
+                const CoopOut r = soft_coop<kCount, kSph, kMix>(
                     gg, masks, true, inv3(rl3(P, ow)), inv3(rl3(ldir, ow)),
                     inv(rld(ldist, ow)), cand_of_lane(cm, ow), rl64(srng.x, ow), h.jump, stack, c);
                 if (lane == ow) {
@@ -2541,7 +2547,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               }
             } else {
               const int uq =
-                  soft_queue<kCount, kSph>(gg, masks, traced_soft, true, P, ldir, ldist, cm, srng, h.jump, stack, c);
+                  soft_queue<kCount, kSph, kMix>(gg, masks, traced_soft, true, P, ldir, ldist, cm, srng, h.jump, stack, c);
               if (traced_soft) unocc = uq;  // (a free lane keeps its 16)
             }
           }
@@ -2707,6 +2713,14 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
 template <bool kCount, bool kStage, bool kPilot, bool kSky>
 __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_kernel(const KParams pk) {
   render_body<BlockBody<kCount, kStage, kPilot, kSky>>(pk);
+}
+// The unstaged render_kernel whose BVH branches (closest_hit / any_hit, kMix)
+// also take leaves of cubes: kernels of their own, picked by launch_render for
+// a tree that has such leaves, so the others keep their code and registers
+// (DESIGN.md §4.2).
+template <bool kCount, bool kPilot, bool kSky>
+__global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_kernel_mix(const KParams pk) {
+  render_body<MixBody<kCount, kPilot, kSky>>(pk);
 }
 // the staged product render with tail helpers (rt_tuning.tail_helpers > 0)
 __global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_kernel_tail(const KParams pk) {
@@ -3026,7 +3040,16 @@ int launch_render(const KParams& pin, bool count, void* stream) {
     q.acc_mode = 0;
     return launch_render(q, true, stream);
   }
-  if (p.work_max) {  // a measuring render (pilot or first frame): its own instantiation (and kernel name)
+  if (p.use_bvh == 2) {  // a tree with leaves of cubes (never staged): render_kernel_mix
+    if (p.work_max)
+      hipLaunchKernelGGL((render_kernel_mix<false, true, false>), g, b, shmem, st, p);
+    else if (count)
+      hipLaunchKernelGGL((render_kernel_mix<true, false, false>), g, b, shmem, st, p);
+    else if (p.sky)
+      hipLaunchKernelGGL((render_kernel_mix<false, false, true>), g, b, shmem, st, p);
+    else
+      hipLaunchKernelGGL((render_kernel_mix<false, false, false>), g, b, shmem, st, p);
+  } else if (p.work_max) {  // a measuring render (pilot or first frame): its own instantiation (and kernel name)
     if (stage)
       hipLaunchKernelGGL((render_kernel<false, true, true, false>), g, b, shmem, st, p);
     else

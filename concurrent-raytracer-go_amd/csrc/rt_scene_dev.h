@@ -11,7 +11,7 @@
 //     per-metallic tables of calculateDirectLighting / traceRay
 //     (renderer.go:193-226, 236-246, 262-287).
 // Small scenes are scanned linearly with wave-uniform (scalar-cache) loads;
-// large sphere scenes use the BVH (bvh.cpp) whose nodes follow the arrays.
+// large scenes use the BVH (bvh.cpp) whose nodes follow the arrays.
 #pragma once
 #include <stdint.h>
 
@@ -99,12 +99,14 @@ struct alignas(16) DSky {  // 240 B
   double pad;
 };
 
-// BVH node over spheres (binned SAH, built on host).  Bounds are float,
-// rounded outward so a box never excludes a sphere point; leaves reference
-// [first, first+count) of the BVH-ordered sphere array.
+// BVH node over spheres and cubes (binned SAH, built on host).  Bounds are
+// float, rounded outward so a box never excludes a point of its primitives;
+// a leaf references [first, first+count) of the BVH-ordered sphere array, or,
+// with kCubeLeafBit (rt_internal.h) set in left_or_first, of the BVH-ordered
+// DBox array (a cube is one primitive).
 struct alignas(16) DBVHNode {  // 32 B
   float lo[3];
-  int32_t left_or_first;  // internal: index of left child (right = left+1); leaf: first sphere
+  int32_t left_or_first;  // internal: index of left child (right = left+1); leaf: first sphere / first cube | kCubeLeafBit
   float hi[3];
   int32_t count;          // 0 = internal node
 };

@@ -95,6 +95,12 @@ constexpr uint32_t kWideBit = 1u << 20;   // ... a wide one (kWfConeK < candidat
 // ends it with the sky's radiance (GetSkyColor, atmosphere.go:100-135) --
 // kept out of the traversal kernel, whose registers it would cost
 constexpr int kSkyMiss = -2;
+// hidx of a triangle hit (the kMix kernels: a tree with leaves of cubes,
+// bvh.cpp): this bit and the triangle's index; a sphere hit is its index
+// alone.  wf_extend leaves such a hit's barycentric u, v in the slot's ox, oy
+// (the ray's origin is dead once its closest hit is known: every later kernel
+// of the bounce works from the hit point, and wf_shade writes the next array).
+constexpr int kTriHit = 1 << 30;
 
 extern __shared__ __attribute__((aligned(16))) unsigned char wf_lds[];
 
@@ -509,8 +515,12 @@ __device__ __forceinline__ bool job_refill(JobSrc& js, int32_t* heads, int n) {
 // tests, same exact-t tie rule).  Wave w owns jobs [n w / W, n (w+1) / W) and
 // refills idle lanes from them.  A hit leaves (sphere, root numerator) for
 // shade1; a miss ends the path with the radiance it has (renderer.go:170-173).
-template <bool kCount, bool kFull>
-__global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
+// kMix (here and in wf_shade1, wf_occlude, wf_cone, wf_shade): the tree has
+// leaves of cubes (kCubeCode in the leaf's code, bvh.cpp); kernels of their
+// own, launched for such a tree only, so the others keep their code.  A cube
+// leaf runs the linear scan's per-cube loop (rt_device.h closest_cube_leaf).
+template <bool kCount, bool kFull, bool kMix>
+__device__ __forceinline__ void extend_body(const WfParams& p) {
   const Dense dn = dense(p.ctl->cur_cnt);
   const int n = dn.start[kWfShards];
   if (n == 0) return;
@@ -532,6 +542,7 @@ __global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
   RayQ r32{};
   float tminf = 0;
   int cur = -1, sp = 0, best_obj = -1, bidx = -1;
+  [[maybe_unused]] double hu = 0, hv = 0;  // (kMix) a triangle hit's barycentrics
   for (;;) {
     const unsigned long long idle = __ballot(!busy);
     if (more && (__popcll(idle) >= kRefill || idle == ~0ull) && js.next >= js.hi)
@@ -556,11 +567,22 @@ __global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
           if (!ray_finite(o, d)) {
             // no box serves a non-finite ray (rt_device.h ray_finite): every
             // sphere gets its exact test, and the walk below starts finished
-            HitSelS hs{0, -1};
-            closest_scan<kCount, true>(p.g, o, d, av, inv_a, hs, c);
-            bidx = hs.idx;
-            best_obj = hs.idx >= 0 ? p.g.spheres[hs.idx].obj : -1;
-            closest = hs.num / av;
+            if constexpr (kMix) {  // ... and every cube
+              HitSel hs{0, 0, 0, -1, 0};
+              const bool any = closest_scan<kCount, false, true>(p.g, o, d, av, inv_a, hs, c);
+              const bool tri = any && hs.is_tri;
+              bidx = !any ? -1 : (tri ? (kTriHit | hs.idx) : hs.idx);
+              best_obj = !any ? -1 : (tri ? p.g.tris[hs.idx].obj : p.g.spheres[hs.idx].obj);
+              closest = tri ? hs.num : hs.num / av;
+              hu = hs.u;
+              hv = hs.v;
+            } else {
+              HitSelS hs{0, -1};
+              closest_scan<kCount, true>(p.g, o, d, av, inv_a, hs, c);
+              bidx = hs.idx;
+              best_obj = hs.idx >= 0 ? p.g.spheres[hs.idx].obj : -1;
+              closest = hs.num / av;
+            }
             cur = -1;
             sp = 0;
             busy = true;
@@ -589,6 +611,20 @@ __global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
     }
     if (busy) {
       descend_x<kCount, kFull>((glb_node*)p.qbvh, lt, p.lds_nodes, r32, tminf, t_hi32(closest), cur, sp, stack, c);
+      if constexpr (kMix) {
+        if (cur != -1 && (cur & kCubeCode) != 0) {  // a leaf of cubes (what is popped waits for the next round)
+          HitSel hs{0, 0, 0, -1, 0};
+          bool got = false;
+          closest_cube_leaf<kCount>(p.g, cur, o, d, inv_dir(d), tmin, closest, best_obj, got, hs, c);
+          if (got) {  // (closest and best_obj are the hit's already)
+            bidx = kTriHit | hs.idx;
+            hu = hs.u;
+            hv = hs.v;
+          }
+          cur = sp == 0 ? -1 : stack[--sp * 64];
+          if (cur != -1) continue;
+        }
+      }
       if (cur != -1 && (cur & 7) != 0) {  // a leaf: the exact Sphere.Hit tests, in hittable order
         const int first = cur >> 3, count = cur & 7;
         DSphere ls[kLeafBatch];
@@ -612,7 +648,14 @@ __global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
         if (best_obj >= 0) {
           // the hit point (HitRecord.P, sphere.go:44: t = the root / a, as
           // kept in `closest`), for shade1, the occlusion kernels and shade
+          // (a triangle's: triangle.go:68, P = o + d t, the same expression)
           const d3 P = o + muls(d, closest);
+          if constexpr (kMix) {
+            if (bidx & kTriHit) {
+              a.ox[slot] = hu;
+              a.oy[slot] = hv;
+            }
+          }
           p.hidx[slot] = bidx;
           p.px[slot] = P.x;
           p.py[slot] = P.y;
@@ -628,12 +671,20 @@ __global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
   }
   flush_counts<kCount>(p, c, kGroupExtend);
 }
+template <bool kCount, bool kFull>
+__global__ RT_TRAV_ATTR void wf_extend(const WfParams p) {
+  extend_body<kCount, kFull, false>(p);
+}
+template <bool kCount, bool kFull>
+__global__ RT_TRAV_ATTR void wf_extend_mix(const WfParams p) {
+  extend_body<kCount, kFull, true>(p);
+}
 
 // ---------------------------------------------------------------- shade1
 // HitRecord of every hit (sphere.go:42-58, as in the megakernel) and one hard
 // shadow ray per lit light (renderer.go:249-256,299-305) into the hard queue.
-template <bool kCount>
-__global__ __launch_bounds__(kWfBlock) void wf_shade1(const WfParams p) {
+template <bool kCount, bool kMix>
+__device__ __forceinline__ void shade1_body(const WfParams& p) {
   __shared__ int s_wave[kWfBlock / 64];
   __shared__ int s_base;
   const Dense dn = dense(p.ctl->cur_cnt);
@@ -670,7 +721,10 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade1(const WfParams p) {
   // inside a glass sphere) is blocked by it, and an occlusion query's answer
   // does not depend on which hittable blocks it, so it is settled here
   // without a traversal (exact: the same Sphere.Hit test).
-  const DSphere* S0 = hit ? &p.g.spheres[p.hidx[slot]] : nullptr;
+  // (kMix: a triangle hit has no such shortcut -- its hard rays are all queued)
+  [[maybe_unused]] bool tri = false;
+  if constexpr (kMix) tri = hit && (p.hidx[slot] & kTriHit) != 0;
+  const DSphere* S0 = hit ? &p.g.spheres[kMix && tri ? 0 : p.hidx[slot]] : nullptr;
   // lights in chunks of 32 (one bit each; any number of lights)
   for (int base = 0; base < p.nl; base += 32) {
     uint32_t lit = 0;
@@ -685,6 +739,13 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade1(const WfParams p) {
           st = 0;
           cnt<kCount>(c, C_LIGHT);
           cnt<kCount>(c, C_SHADOW);
+          if constexpr (kMix) {
+            if (tri) {
+              lit |= 1u << (li - base);
+              p.lstate[slot * p.nl + li] = st;
+              continue;
+            }
+          }
           cnt<kCount>(c, C_SPH);
           const double a = len2(ldir);
           double num;
@@ -701,6 +762,14 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade1(const WfParams p) {
   }
   flush_counts<kCount>(p, c);
 }
+template <bool kCount>
+__global__ __launch_bounds__(kWfBlock) void wf_shade1(const WfParams p) {
+  shade1_body<kCount, false>(p);
+}
+template <bool kCount>
+__global__ __launch_bounds__(kWfBlock) void wf_shade1_mix(const WfParams p) {
+  shade1_body<kCount, true>(p);
+}
 
 // ---------------------------------------------------------------- occlude
 // Persistent any-hit traversal of the queued shadow rays (hitWorld as used by
@@ -709,8 +778,9 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade1(const WfParams p) {
 // queued point p (renderer.go:316-318) and a blocked ray adds 1 to its
 // (path, light) count; hard: the ray is lightDir and a blocked ray sets
 // kHardBit.
-template <bool kCount, bool kSoft, bool kFull, bool kB4>
+template <bool kCount, bool kSoft, bool kFull, bool kB4, bool kMix = false>
 __device__ __forceinline__ void occlude_body(const WfParams& p) {
+  static_assert(!(kMix && kB4), "the 4-wide tree is walked for trees of spheres only");
   const Dense dn = dense(kSoft ? p.ctl->soft_cnt : p.ctl->hard_cnt);
   const int n = dn.start[kWfShards];
   if (n == 0) return;
@@ -770,6 +840,18 @@ __device__ __forceinline__ void occlude_body(const WfParams& p) {
             double num;
             hit = sphere_query(p.g.spheres[i], o, d, av, inv_a, tmin, tmax, num) != 0;
           }
+          if constexpr (kMix) {  // ... and every cube (any_hit's linear scan)
+            const d3 idx = inv_dir(d);
+            for (int j = 0; j < p.g.nb && !hit; ++j) {
+              const DBox& B = p.g.boxes[j];
+              if (!ray_box(B, o, idx, tmin, tmax)) continue;
+              for (int i = B.first; i < B.first + B.count && !hit; ++i) {
+                cnt<kCount>(c, C_TRI);
+                double t, u, v;
+                hit = tri_test(p.g.tris[i], o, d, tmin, tmax, t, u, v);
+              }
+            }
+          }
           if (hit) {
             if constexpr (kSoft)
               atomicAdd(&p.lstate[key], 1u);
@@ -796,7 +878,14 @@ __device__ __forceinline__ void occlude_body(const WfParams& p) {
       else
         descend<kCount, kFull>((glb_node*)p.qbvh, lt, p.lds_nodes, r32, tminf, tmaxf, cur, sp, stack, c);
       bool blocked = false;
-      if (cur != -1 && (cur & 7) != 0) {  // (a leaf; an internal node: the descent paused, descend4)
+      bool cubes = false;  // (kMix) the leaf holds cubes
+      if constexpr (kMix) cubes = cur != -1 && (cur & kCubeCode) != 0;
+      if (cubes) {
+        if constexpr (kMix) {
+          blocked = any_cube_leaf<kCount>(p.g, cur, o, d, inv_dir(d), tmin, tmax, c);
+          cur = sp == 0 ? -1 : stack[--sp * 64];
+        }
+      } else if (cur != -1 && (cur & 7) != 0) {  // (a leaf; an internal node: the descent paused, descend4)
         const int first = cur >> 3, count = cur & 7;
         DSphere ls[kLeafBatch];
         load_leaf(p.g.spheres, first, count, ls);
@@ -821,6 +910,10 @@ __device__ __forceinline__ void occlude_body(const WfParams& p) {
 template <bool kCount, bool kSoft, bool kFull>
 __global__ RT_TRAV_ATTR void wf_occlude(const WfParams p) {
   occlude_body<kCount, kSoft, kFull, false>(p);
+}
+template <bool kCount, bool kSoft, bool kFull>
+__global__ RT_TRAV_ATTR void wf_occlude_mix(const WfParams p) {
+  occlude_body<kCount, kSoft, kFull, false, true>(p);
 }
 template <bool kCount, bool kSoft>  // over the 4-wide tree (WfParams.use4)
 __global__ RT_TRAV_ATTR void wf_occlude4(const WfParams p) {
@@ -920,6 +1013,18 @@ __device__ __forceinline__ bool cone_keeps(const DSphere& S, d3 P, d3 u, double 
   const double dc2 = len2(v);
   const double dc = (double)__builtin_amdgcn_sqrtf((float)dc2);
   const double ra = fabs(S.r) * (1.0 + 1e-5) + 1e-5 * dc + 1e-12;
+  const double tl = (double)__builtin_amdgcn_sqrtf((float)fmax(dc2 - ra * ra, 0.0));
+  const bool miss =
+      dc > ra && (dc - ra > ldist * (1.0 + 1e-5) + 1e-9 || dot(v, u) < 0.99498 * tl - 0.1 * ra - 1e-5 * dc);
+  return !miss;
+}
+
+// (kMix) the same test of a cube's bounding sphere
+__device__ __forceinline__ bool cone_keeps_ball(const double* cc, double r, d3 P, d3 u, double ldist) {
+  const d3 v = ld3(cc) - P;
+  const double dc2 = len2(v);
+  const double dc = (double)__builtin_amdgcn_sqrtf((float)dc2);
+  const double ra = fabs(r) * (1.0 + 1e-5) + 1e-5 * dc + 1e-12;
   const double tl = (double)__builtin_amdgcn_sqrtf((float)fmax(dc2 - ra * ra, 0.0));
   const bool miss =
       dc > ra && (dc - ra > ldist * (1.0 + 1e-5) + 1e-9 || dot(v, u) < 0.99498 * tl - 0.1 * ra - 1e-5 * dc);
@@ -1028,8 +1133,15 @@ __global__ __launch_bounds__(kWfBlock) void wf_conegen(const WfParams p) {
 // kWfConeK (one more ends the walk: the cone's rays are traced instead).
 // The hit sphere itself is left out as in cone_candidates (rt_kernel.hip)
 // when the cone leaves its front face at a clear angle.
-template <bool kCount, bool kFull, bool kB4>
+// kMix: the lists stay lists of spheres.  A cone that reaches a cube whose
+// bounding sphere (DBox.bc, br) passes the same test ends as "too many
+// candidates": its 16 rays are traced (wf_occlude<soft>), which is exact; a
+// cone that reaches no such cube cannot be blocked by one.  The hit cube is
+// not left out (its bounding sphere holds the hit point), so a cone that
+// starts on a cube is always traced.
+template <bool kCount, bool kFull, bool kB4, bool kMix = false>
 __device__ __forceinline__ void cone_body(const WfParams& p) {
+  static_assert(!(kMix && kB4), "the 4-wide tree is walked for trees of spheres only");
   const Dense dn = dense(p.ctl->cone_cnt);
   const int n = dn.start[kWfShards];
   if (n == 0) return;
@@ -1060,10 +1172,16 @@ __device__ __forceinline__ void cone_body(const WfParams& p) {
         const uint32_t slot = key / (uint32_t)p.nl, li = key - slot * (uint32_t)p.nl;
         P = ld_P(p, (int)slot);
         light_vec(p.lights[li], P, u, ldist);
-        const DSphere& S0 = p.g.spheres[p.hidx[slot]];
-        const d3 outward = divs(P - ld3(S0.c), S0.r);
-        const bool self_out = dot(ld_d(p.cur, slot), outward) < 0 && dot(outward, u) >= 0.1015;
-        excl = self_out ? S0.obj : -1;
+        bool tri = false;
+        if constexpr (kMix) tri = (p.hidx[slot] & kTriHit) != 0;
+        if (tri) {
+          excl = -1;
+        } else {
+          const DSphere& S0 = p.g.spheres[p.hidx[slot]];
+          const d3 outward = divs(P - ld3(S0.c), S0.r);
+          const bool self_out = dot(ld_d(p.cur, slot), outward) < 0 && dot(outward, u) >= 0.1015;
+          excl = self_out ? S0.obj : -1;
+        }
         bool ok;
         k = cone_q(p, P, u, ldist, ok);
         // (a cone whose bounds cannot be evaluated is not walked: "too many
@@ -1083,7 +1201,18 @@ __device__ __forceinline__ void cone_body(const WfParams& p) {
         cone_descend4<kCount>(lt, k, cur, sp, stack, c);
       else
         cone_descend<kCount, kFull>((glb_node*)p.qbvh, lt, p.lds_nodes, k, cur, sp, stack, c);
-      if (cur != -1 && (cur & 7) != 0) {  // (a leaf; an internal node: the walk paused, cone_descend4)
+      bool cubes = false;  // (kMix) the leaf holds cubes
+      if constexpr (kMix) cubes = cur != -1 && (cur & kCubeCode) != 0;
+      if (cubes) {
+        if constexpr (kMix) {
+          const int first = (cur & ~kCubeCode) >> 3, count = cur & 7;
+          for (int j = first; j < first + count; ++j) {
+            const DBox& B = p.g.boxes[j];
+            if (cone_keeps_ball(B.bc, B.br, P, u, ldist)) found = kWfConeWide + 1;
+          }
+          cur = found > kWfConeWide || sp == 0 ? -1 : stack[--sp * 64];
+        }
+      } else if (cur != -1 && (cur & 7) != 0) {  // (a leaf; an internal node: the walk paused, cone_descend4)
         const int first = cur >> 3, count = cur & 7;
         DSphere ls[kLeafBatch];
         load_leaf(p.g.spheres, first, count, ls);
@@ -1118,6 +1247,10 @@ __device__ __forceinline__ void cone_body(const WfParams& p) {
 template <bool kCount, bool kFull>
 __global__ RT_TRAV_ATTR void wf_cone(const WfParams p) {
   cone_body<kCount, kFull, false>(p);
+}
+template <bool kCount, bool kFull>
+__global__ RT_TRAV_ATTR void wf_cone_mix(const WfParams p) {
+  cone_body<kCount, kFull, false, true>(p);
 }
 template <bool kCount>  // over the 4-wide tree (WfParams.use4)
 __global__ RT_TRAV_ATTR void wf_cone4(const WfParams p) {
@@ -1496,8 +1629,8 @@ __global__ __launch_bounds__(kWfBlock) void wf_widetest(const WfParams p) {
 // Material.Scatter and the traceRay combination (renderer.go:181-226).
 // Finished paths write their sample's radiance; survivors are appended to the
 // workgroup's shard of the next path array.
-template <bool kCount>
-__global__ __launch_bounds__(kWfBlock) void wf_shade(const WfParams p) {
+template <bool kCount, bool kMix>
+__device__ __forceinline__ void shade_body(const WfParams& p) {
   __shared__ int s_wave[kWfBlock / 64];
   __shared__ int s_base;
   const Dense dn = dense(p.ctl->cur_cnt);
@@ -1519,11 +1652,28 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade(const WfParams p) {
       P = mk(p.px[slot], p.py[slot], p.pz[slot]);
       const d3 d = ld_d(a, slot);
       // HitRecord (sphere.go:42-58): the outward normal at P, flipped to face the ray
-      const DSphere& S0 = p.g.spheres[p.hidx[slot]];
+      [[maybe_unused]] bool tri = false;
+      if constexpr (kMix) tri = (p.hidx[slot] & kTriHit) != 0;
+      const DSphere& S0 = p.g.spheres[kMix && tri ? 0 : p.hidx[slot]];
       const d3 outward = divs(P - ld3(S0.c), S0.r);
-      const bool front = dot(d, outward) < 0;
-      const d3 N = front ? outward : neg(outward);
+      bool front = dot(d, outward) < 0;
+      d3 N = front ? outward : neg(outward);
       const DMat* __restrict__ m = p.mats + S0.mat;
+      if constexpr (kMix) {
+        if (tri) {
+          // triangle.go:68-81 with the megakernel's expressions (rt_kernel.hip
+          // render_body); u, v from wf_extend (kTriHit).  (The sphere record
+          // above was formed from sphere 0 of the scene buffer and is dropped.)
+          const DTri& T0 = p.g.tris[p.hidx[slot] & ~kTriHit];
+          const double hu = a.ox[slot], hv = a.oy[slot];
+          const double w = 1.0 - hu - hv;
+          const d3 n = ld3(T0.n);
+          N = normalize((muls(n, w) + muls(n, hu)) + muls(n, hv));
+          front = dot(d, N) < 0;
+          if (!front) N = neg(N);
+          m = p.mats + T0.mat;
+        }
+      }
       T = mk(a.tx[slot], a.ty[slot], a.tz[slot]);
       L = mk(a.lx[slot], a.ly[slot], a.lz[slot]);
       rng.x = a.rng[slot];
@@ -1576,6 +1726,14 @@ __global__ __launch_bounds__(kWfBlock) void wf_shade(const WfParams p) {
   const int q = block_append(cont ? 1 : 0, &p.ctl->next_cnt[shard * 32], s_wave, &s_base);
   if (cont) store_path(p.next, (size_t)shard * p.shard_cap + q, P, nd, T, L, rng.x, sid, depth);
   flush_counts<kCount>(p, c);
+}
+template <bool kCount>
+__global__ __launch_bounds__(kWfBlock) void wf_shade(const WfParams p) {
+  shade_body<kCount, false>(p);
+}
+template <bool kCount>
+__global__ __launch_bounds__(kWfBlock) void wf_shade_mix(const WfParams p) {
+  shade_body<kCount, true>(p);
 }
 
 // ---------------------------------------------------------------- regen
@@ -1780,7 +1938,7 @@ static int enqueue_regen_book(const WfParams& p, hipStream_t st, const hipEvent_
 }
 
 // the traversal kernels of one bounce: closest hit, hard and soft occlusion
-template <bool kCount, bool kFull>
+template <bool kCount, bool kFull, bool kMix = false>
 static void enqueue_trav(const WfParams& p, hipStream_t st, int which) {
   const dim3 bt(p.trav_block);
   const size_t sh = trav_shmem(p);
@@ -1790,7 +1948,7 @@ static void enqueue_trav(const WfParams& p, hipStream_t st, int which) {
   struct Grids {
     int ext = 0, occ_h = 0, occ_s = 0, cone = 0;
   };
-  if (p.use4 && which != 0) {  // occlusion and cone walks over the 4-wide tree
+  if (!kMix && p.use4 && which != 0) {  // occlusion and cone walks over the 4-wide tree
     const size_t sh4 = (size_t)p.trav_block * p.stack4 * sizeof(int) + (size_t)p.nodes4 * sizeof(uint4);
     static std::mutex mu4;
     static std::map<std::tuple<int, size_t, int>, Grids> cache4;
@@ -1826,13 +1984,27 @@ static void enqueue_trav(const WfParams& p, hipStream_t st, int which) {
     auto it = cache.find(key);
     if (it == cache.end()) {
       Grids c;
-      c.ext = resident_grid(wf_extend<kCount, kFull>, p.trav_block, sh);
-      c.occ_h = resident_grid(wf_occlude<kCount, false, kFull>, p.trav_block, sh);
-      c.occ_s = resident_grid(wf_occlude<kCount, true, kFull>, p.trav_block, sh);
-      c.cone = resident_grid(wf_cone<kCount, kFull>, p.trav_block, sh);
+      if constexpr (kMix) {
+        c.ext = resident_grid(wf_extend_mix<kCount, kFull>, p.trav_block, sh);
+        c.occ_h = resident_grid(wf_occlude_mix<kCount, false, kFull>, p.trav_block, sh);
+        c.occ_s = resident_grid(wf_occlude_mix<kCount, true, kFull>, p.trav_block, sh);
+        c.cone = resident_grid(wf_cone_mix<kCount, kFull>, p.trav_block, sh);
+      } else {
+        c.ext = resident_grid(wf_extend<kCount, kFull>, p.trav_block, sh);
+        c.occ_h = resident_grid(wf_occlude<kCount, false, kFull>, p.trav_block, sh);
+        c.occ_s = resident_grid(wf_occlude<kCount, true, kFull>, p.trav_block, sh);
+        c.cone = resident_grid(wf_cone<kCount, kFull>, p.trav_block, sh);
+      }
       it = cache.emplace(key, c).first;
     }
     g = it->second;
+  }
+  if constexpr (kMix) {
+    if (which == 0) hipLaunchKernelGGL((wf_extend_mix<kCount, kFull>), dim3(g.ext), bt, sh, st, p);
+    if (which == 1) hipLaunchKernelGGL((wf_occlude_mix<kCount, false, kFull>), dim3(g.occ_h), bt, sh, st, p);
+    if (which == 2) hipLaunchKernelGGL((wf_occlude_mix<kCount, true, kFull>), dim3(g.occ_s), bt, sh, st, p);
+    if (which == 3) hipLaunchKernelGGL((wf_cone_mix<kCount, kFull>), dim3(g.cone), bt, sh, st, p);
+    return;
   }
   if (which == 0) hipLaunchKernelGGL((wf_extend<kCount, kFull>), dim3(g.ext), bt, sh, st, p);
   if (which == 1) hipLaunchKernelGGL((wf_occlude<kCount, false, kFull>), dim3(g.occ_h), bt, sh, st, p);
@@ -1849,8 +2021,13 @@ static int enqueue_bounce(const WfParams& p, hipStream_t st, const hipEvent_t* e
   const long long live = std::min<long long>((long long)kWfShards * p.shard_cap, std::max(p.live_bound, 1));
   const dim3 gd((unsigned)((live + kWfBlock - 1) / kWfBlock));
   const bool full = p.lds_nodes >= p.bvh_nodes;
+  const bool mix = p.g.use_bvh == 2;  // the tree has leaves of cubes: the kMix kernels (binary tree only)
   auto trav = [&](int which) {
-    if (full)
+    if (mix && full)
+      enqueue_trav<kCount, true, true>(p, st, which);
+    else if (mix)
+      enqueue_trav<kCount, false, true>(p, st, which);
+    else if (full)
       enqueue_trav<kCount, true>(p, st, which);
     else
       enqueue_trav<kCount, false>(p, st, which);
@@ -1858,7 +2035,10 @@ static int enqueue_bounce(const WfParams& p, hipStream_t st, const hipEvent_t* e
   mark(ev, kWfExtend, st);
   trav(0);
   mark(ev, kWfShade1, st);
-  hipLaunchKernelGGL((wf_shade1<kCount>), gd, b, 0, st, p);
+  if (mix)
+    hipLaunchKernelGGL((wf_shade1_mix<kCount>), gd, b, 0, st, p);
+  else
+    hipLaunchKernelGGL((wf_shade1<kCount>), gd, b, 0, st, p);
   mark(ev, kWfHard, st);
   if (p.nl > 0) trav(1);
   mark(ev, kWfCone, st);
@@ -1879,7 +2059,10 @@ static int enqueue_bounce(const WfParams& p, hipStream_t st, const hipEvent_t* e
   mark(ev, kWfSoft, st);
   if (p.nl > 0 && p.soft) trav(2);
   mark(ev, kWfShade, st);
-  hipLaunchKernelGGL((wf_shade<kCount>), gd, b, 0, st, p);
+  if (mix)
+    hipLaunchKernelGGL((wf_shade_mix<kCount>), gd, b, 0, st, p);
+  else
+    hipLaunchKernelGGL((wf_shade<kCount>), gd, b, 0, st, p);
   mark(ev, kWfRegen, st);
   return enqueue_regen_book<kCount>(p, st, ev, active);
 }

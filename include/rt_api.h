@@ -336,8 +336,11 @@ int rt_context_create(int32_t device, rt_context** out);
 void rt_context_destroy(rt_context* ctx);
 
 /* Flatten (GetHittables, scene.go:59-90; createCube, scene.go:150-190) and
- * upload the scene to device memory.  Builds the BVH when the scene is
- * large (or when force_bvh > 0; force_bvh < 0 forbids it).  A scene with a
+ * upload the scene to device memory.  Builds the BVH, one tree over the
+ * spheres and the cubes (a cube is one primitive: its box, then its 12
+ * triangles), when the scene is large: more than 64 spheres, or more than 64
+ * cubes (or when force_bvh > 0; force_bvh < 0 forbids it).  The image is the
+ * linear scan's bit for bit on either RT_PATH_*.  A scene with a
  * sphere whose centre or radius is not finite never gets a BVH, forced or
  * not: such a sphere has no bounding box (a NaN one is hit by every ray), and
  * the linear scan renders it whatever the number of spheres.  Non-finite
