@@ -264,6 +264,26 @@ int rt_camera_frame(const rt_camera* cam, int32_t model, int32_t w, int32_t h, d
   return RT_OK;
 }
 
+int rt_scene_cone_rows(const rt_scene* scene, int32_t force_bvh, uint64_t* out, size_t capacity) {
+  int rc = validate_scene(scene);
+  if (rc) return rc;
+  const size_t n = (size_t)scene->num_lights * (size_t)scene->num_objects;
+  if (n > 0 && (!out || capacity < n)) {
+    set_error("cone rows: out holds " + std::to_string(out ? capacity : 0) + " rows, the scene has " + std::to_string(n));
+    return RT_E_INVALID;
+  }
+  FlatScene f;
+  flatten_scene(*scene, &f);
+  // (rt_context_set_scene's rule for a tree, and its default build)
+  if ((force_bvh > 0 || (force_bvh == 0 && (f.spheres.size() > 64 || f.boxes.size() > (size_t)kAutoBvhCubes))) &&
+      spheres_finite(f))
+    build_bvh(&f, 0, 0);
+  std::vector<unsigned long long> rows;
+  cone_rows(f, &rows);
+  for (size_t i = 0; i < n; ++i) out[i] = rows[i];
+  return RT_OK;
+}
+
 const char* rt_last_error(void) { return g_last_error.c_str(); }
 
 // pinned scene staging made by rt_context_create (grown when a scene needs more)
@@ -398,7 +418,13 @@ int rt_context_set_scene(rt_context* c, const rt_scene* s, int32_t force_bvh) {
   size_t off_x = off_t + al(f.tris.size() * sizeof(DTri));
   size_t off_m = off_x + al(f.boxes.size() * sizeof(DBox));
   size_t off_l = off_m + al(f.mats.size() * sizeof(DMat));
-  size_t off_j = off_l + al(f.lights.size() * sizeof(DLight));
+  // shadow-cone rows of a scene of spheres alone, right behind the lights so
+  // that they are staged with them (the spheres-only stream kernels read them)
+  std::vector<unsigned long long> rows;
+  if (!f.spheres.empty() && f.tris.empty() && f.boxes.empty() && !f.lights.empty() && cone_masks_apply(f))
+    cone_rows(f, &rows);
+  size_t off_r = off_l + f.lights.size() * sizeof(DLight);  // (a multiple of 16)
+  size_t off_j = off_l + al(f.lights.size() * sizeof(DLight) + rows.size() * sizeof(unsigned long long));
   size_t off_b = off_j + al(kJump * 2 * sizeof(uint64_t));
   size_t off_q = off_b + al(f.bvh.size() * sizeof(DBVHNode));
   size_t off_q4 = off_q + al(f.qbvh.size() * sizeof(DQNode));
@@ -417,6 +443,7 @@ int rt_context_set_scene(rt_context* c, const rt_scene* s, int32_t force_bvh) {
   memcpy(host + off_x, f.boxes.data(), f.boxes.size() * sizeof(DBox));
   memcpy(host + off_m, f.mats.data(), f.mats.size() * sizeof(DMat));
   memcpy(host + off_l, f.lights.data(), f.lights.size() * sizeof(DLight));
+  memcpy(host + off_r, rows.data(), rows.size() * sizeof(unsigned long long));
   {
     uint64_t* jt = reinterpret_cast<uint64_t*>(host + off_j);
     uint64_t a = 1, cc = 0;  // x_{i+j} = A_j x_i + C_j, built incrementally (rt_pcg_jump_coeffs)
@@ -453,6 +480,7 @@ int rt_context_set_scene(rt_context* c, const rt_scene* s, int32_t force_bvh) {
   // closest-hit scan among helper lanes and merges by distance, closest_wide,
   // which equals the sequential scan only while no hit distance is NaN)
   c->stage_bytes = (f.bvh.empty() && off_j <= 48 * 1024 && spheres_finite(f)) ? (int32_t)off_j : 0;
+  c->cone_rows_off = (c->stage_bytes > 0 && !rows.empty()) ? (int32_t)off_r : 0;
   c->have_scene = true;
   c->scene_gen += 1;
   return RT_OK;

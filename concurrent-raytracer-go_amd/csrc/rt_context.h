@@ -104,6 +104,7 @@ struct rt_context {
   std::vector<unsigned long long> masks_host;  // per local tile primary-ray masks
   unsigned long long* d_masks = nullptr;       // (inside d.sched)
   int32_t stage_bytes = 0;  // scene prefix staged into LDS per workgroup (0 = none)
+  int32_t cone_rows_off = 0;  // the staged shadow-cone rows' offset in it (KParams::cone_rows_off; 0 = none)
   rtgo::WfCtl* wf_host = nullptr;  // pinned ring of kWfRing snapshots of d.wf_ctl
   hipEvent_t wf_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   // tile partition (rt_context_set_partition): its data; d.part holds every
@@ -283,6 +284,7 @@ inline void base_params(const rt_context* c, int w, int h, const rt_settings* st
   // LDS staging of the scene prefix + BVH stack placement
   p.stage_src = c->d.scene.p;
   p.stage_bytes = c->tun.stage ? c->stage_bytes : 0;
+  p.cone_rows_off = p.stage_bytes > 0 ? c->cone_rows_off : 0;
   p.stack_off = (p.stage_bytes + 15) & ~15;
   p.stack_depth = std::max(1, f.bvh_depth);
 }

@@ -71,6 +71,13 @@ void sky_presets(DSky out[kSkies]);
 
 // GetHittables + createCube + material constructors (scene.go:59-190).
 void flatten_scene(const rt_scene& s, FlatScene* out);
+// Shadow-cone rows (scene_flat.cpp; rt_scene_cone_rows, include/rt_api.h):
+// rows[light * fs.objects + hittable], bit b clear when sphere b (its index in
+// fs.spheres) can never be a shadow-cone candidate of a hit on that hittable
+// under that light.  Full rows (~0) without shadow-cone masks (cone_masks_apply:
+// a tree, or more than 64 spheres or triangles), for cubes and non-finite scenes.
+bool cone_masks_apply(const FlatScene& fs);
+void cone_rows(const FlatScene& fs, std::vector<unsigned long long>* rows);
 // Binned-SAH BVH over out->spheres and out->boxes, a cube being one primitive
 // (reorders both arrays; the triangles stay).  Leaves hold one kind.
 // bins / leaf: SAH bins per axis and spheres per leaf at most (0: defaults);
@@ -322,7 +329,12 @@ struct KParams {
   int32_t tail_cap, tail_helpers, tail_kmax, tail_dmin;
   uint32_t tail_epoch;
   int32_t tail_every_mask;  // the drain's iterations between export checks - 1 (a power of 2 - 1)
-  int32_t tail_pos, _tpad2; // the helpers are workgroups [tail_pos, tail_pos + tail_helpers) of the grid
+  int32_t tail_pos;         // the helpers are workgroups [tail_pos, tail_pos + tail_helpers) of the grid
+  // shadow-cone rows of a scene of spheres alone (cone_rows: [light][sphere]):
+  // their byte offset in the staged prefix (after the lights), 0: none.  Read
+  // by the spheres-only stream kernels.  (In the struct's former tail padding:
+  // StreamKArgs places StreamParams behind KParams, and no offset of either moves.)
+  int32_t cone_rows_off;
 };
 
 // ---- streamed launches: the samples of the live pixels of

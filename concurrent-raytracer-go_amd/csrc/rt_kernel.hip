@@ -321,8 +321,12 @@ __device__ __forceinline__ bool closest_wide(const Geo& g, bool need, unsigned l
 
 // cone_candidates (spheres only) with helpers: each helper tests its
 // spheres, the group ORs the bits.  Same tests, same mask.
+// (kRows, the spheres-only stream kernels: a helper tests a sphere only if
+// its owner's shadow-cone row -- `row`, cone_row below -- has it)
+template <bool kRows = false>
 __device__ __forceinline__ unsigned long long cone_wide(const Geo& g, bool need, unsigned long long qmask, int nq,
-                                                        d3 P, d3 N, bool front, int self, d3 ldir, double ldist) {
+                                                        d3 P, d3 N, bool front, int self, d3 ldir, double ldist,
+                                                        unsigned long long row = ~0ull) {
   __shared__ int owner_tab2[16];
   const int lane = (int)(threadIdx.x & 63);
   int ow, k;
@@ -333,10 +337,15 @@ __device__ __forceinline__ unsigned long long cone_wide(const Geo& g, bool need,
   const double dist = __shfl(ldist, ow);
   const bool self_out = __shfl((int)(front && dot(N, ldir) >= KC(0.1015)), ow) != 0;
   const int selfo = __shfl(self, ow);
+  unsigned long long rowo = ~0ull;
+  if constexpr (kRows) rowo = __shfl(row, ow);
   unsigned long long m = 0;
   if (helper) {
     for (int i = k; i < g.ns; i += S) {
       const DSphere& Sp = g.spheres[i];
+      if constexpr (kRows) {
+        if (!((rowo >> i) & 1)) continue;
+      }
       if (self_out && Sp.obj == selfo && Sp.r > 0) continue;
       if (in_cone(Sp.c, Sp.r, Po, Lo, dist)) m |= 1ull << i;
     }
@@ -663,6 +672,30 @@ __device__ __forceinline__ Hot hot(KArg k) {
 template <bool kStage, bool kSph = false>
 __device__ __forceinline__ Hot hot() {
   return hot<kStage, kSph>(fresh());
+}
+
+// Shadow-cone rows (the spheres-only stream kernels).  `row`
+// is the lane's row of KParams::cone_rows_off for (light, self): the spheres
+// that a hit on `self` can ever hold in its cone under that light, a superset
+// of what in_cone admits for any P on it (scene_flat.cpp cone_rows), so the
+// mask is cone_candidates' bit for bit.  A sphere in no active lane's row
+// costs the wave one ballot and no in_cone.
+__device__ __forceinline__ unsigned long long cone_row(KArg k, int li, int self) {
+  const int off = k->cone_rows_off;
+  if (off == 0) return ~0ull;
+  return reinterpret_cast<const unsigned long long*>(dyn_lds + off)[li * k->ns + self];
+}
+__device__ __forceinline__ Kind<true>::C cone_candidates_rows(const Geo& p, d3 P, d3 N, bool front, int self, d3 ldir,
+                                                              double ldist, unsigned long long row) {
+  const bool sphere_out = front && dot(N, ldir) >= KC(0.1015);
+  Kind<true>::C m{};
+  for (int i = 0; i < p.ns; ++i) {
+    const DSphere& S = p.spheres[i];
+    const bool mine = ((row >> i) & 1) != 0 && !(sphere_out && S.obj == self && S.r > 0);
+    if (__ballot(mine) == 0) continue;
+    if (mine && in_cone(S.c, S.r, P, ldir, ldist)) m.s |= 1ull << i;
+  }
+  return m;
 }
 
 // Camera ray of sample s of pixel (x, y): tracePixel's jitter
@@ -2474,7 +2507,12 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
               const unsigned long long cq = __ballot(hard);
               const int ncq = __popcll(cq);
               if (ncq > 0 && ncq <= 16) {
-                const unsigned long long ms = cone_wide(gg, hard, cq, ncq, P, N, front, self, ldir, ldist);
+                unsigned long long ms;
+                if constexpr (kSph)
+                  ms = cone_wide<true>(gg, hard, cq, ncq, P, N, front, self, ldir, ldist,
+                                       hard ? cone_row(fresh(), li, self) : 0ull);
+                else
+                  ms = cone_wide(gg, hard, cq, ncq, P, N, front, self, ldir, ldist);
                 if (hard) {
                   cm = CandK{};
                   cm.s = ms;
@@ -2484,7 +2522,12 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             }
           }
           if (hard) {
-            if (masks && !wide_c) cm = cone_candidates<kSph>(gg, P, N, front, self, ldir, ldist);
+            if constexpr (kSph) {
+              if (masks && !wide_c)
+                cm = cone_candidates_rows(gg, P, N, front, self, ldir, ldist, cone_row(fresh(), li, self));
+            } else {
+              if (masks && !wide_c) cm = cone_candidates<kSph>(gg, P, N, front, self, ldir, ldist);
+            }
             if constexpr (kCount) {
               const unsigned long long s0 = c.v[C_SPH], t0 = c.v[C_TRI];
               occl = shadow_blocked<kCount, kSph, kMix>(gg, masks, P, ldir, ldist, cm, stack, c);  // hard shadow ray

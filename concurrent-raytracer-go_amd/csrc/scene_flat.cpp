@@ -268,6 +268,112 @@ void flatten_scene(const rt_scene& s, FlatScene* fs) {
   fs->objects = s.num_objects;
 }
 
+// ---------------------------------------------------------------- shadow-cone rows
+// Which spheres can ever be a shadow-cone candidate (rt_kernel.hip in_cone)
+// of a hit on sphere A under light L?  The hit point P lies on A, so every
+// shadow ray of (A, L) stays in one solid that depends on the scene alone,
+// and a sphere clear of it is never admitted.
+//
+// What in_cone admits.  With v = c_B - P, dc = |v|, ra its inflated radius,
+// sin(beta) = ra / dc, theta = angle(v, ldir), l = ldist (1 + 1e-5) + 1e-9:
+//   inside: dc <= ra;   or   dc - ra <= l  and  theta <= alpha~ + beta,
+// alpha~ = asin(0.1) + d.  d covers the slack of `meets`: dividing it by dc,
+//   cos(theta) >= 0.99498 cos(beta) (1 - 2e-7) - 0.1 sin(beta) - 1e-5 (1 + 2e-7)
+//              >= cos(alpha' + beta) - 1.77e-5
+// (the binary32 roots are 2e-7 wide; |(0.99498, 0.1)| = 1 - 7.4e-6; alpha' =
+// atan(0.1 / 0.99498) = asin(0.1) + 7e-8), and sin(alpha' + beta) >= 0.0999
+// turns 1.77e-5 of cosine into d <= 1.8e-4 rad.
+// Let S be the sector {P + s u : 0 <= s <= l, angle(u, ldir) <= alpha~}.
+//   inside:            P is in S and |c_B - P| <= ra;
+//   theta <= alpha~:   P + min(dc, l) v/dc is in S, max(0, dc - l) <= ra away;
+//   else, phi = theta - alpha~ <= beta and w the cone's edge towards v:
+//     dc cos(phi) <= l:  P + dc cos(phi) w is in S, dc sin(phi) <= ra away;
+//     dc cos(phi) >  l:  the far corner P + l w is
+//       sqrt((dc sin(phi))^2 + (dc cos(phi) - l)^2) <= sqrt(2) ra away,
+//       since 0 < dc cos(phi) - l <= dc - (dc - ra) = ra.
+// So an admitted B has dist(c_B, S) <= ra, or is within sqrt(2) ra of a far
+// corner of S.
+//
+// The solid.  P is within RA = |r_A| + eP of c_A (eP below).  A point of S
+// at ray parameter s = tau * ldist is 2 sin(alpha~ / 2) s <= 0.100306 s from
+// the axis point a = P + tau (L - P), and ldist <= D + RA, D = |L - c_A|.
+//   tau <= 1: a is (1 - tau) RA from c(tau) = (1 - tau) c_A + tau L, so the
+//     point is in the ball around c(tau) of radius RA + tau (kK (D + RA) - RA);
+//   1 < tau <= l / ldist <= 1 + 2e-5 (ldist >= 0.001 for a lit light): a is
+//     2e-5 (D + RA) from L, the point within (0.100306 (1 + 2e-5) + 2e-5)
+//     (D + RA) <= kK (D + RA) of L: the ball of tau = 1, far corners included.
+// kK = 0.1004 leaves 7e-5 over both.  f(t) = |c_B - c(t)| - radius(t) is
+// convex in t, so for any t in [0, 1] its tangent bounds it from below:
+//   min f >= f(t) + min(-t f'(t), (1 - t) f'(t)),
+// evaluated at the stationary point of the closed form (clamped to [0, 1]);
+// a badly rounded t only loosens the bound, it stays one.
+//
+// Margins.  ra <= |r_B| (1 + 1e-5) + 1e-5 (1 + 1e-6) (|c_B - c_A| + RA) + 1e-12
+// (dc <= |c_B - c_A| + RA; 1e-6 for the binary32 root of dc).  eP = 2e-7 E,
+// E the scene's extent (centres + radii, lights, camera): a hit point o + t d
+// has |o - c| <= 2 E, its discriminant an absolute error below 1e-15 a
+// |o - c|^2, so the root moves P by at most sqrt(1e-15) |o - c| < 7e-8 E;
+// the roundings of o + t d are nine orders below that.  This arithmetic is
+// binary64: 1e-9 of the lengths involved covers it a million times over.
+// Scenes of extent beyond 1e15 (binary32 roots of squares overflow) or below
+// 1e-100 (squares underflow) and non-finite scenes get full rows.
+namespace {
+constexpr double kConeK = 0.1004;
+double vdot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+double vnorm(v3 a) { return sqrt(vdot(a, a)); }
+v3 vscale(v3 a, double s) { return mk(a.x * s, a.y * s, a.z * s); }
+
+// sphere B is provably clear of the solid of (hit sphere A, light L)
+bool cone_clear(const DSphere& A, const DSphere& B, v3 L, double E) {
+  const double RA = fabs(A.r) + 2e-7 * E;
+  const v3 w = sub(L, arr(A.c)), q = sub(arr(B.c), arr(A.c));
+  const double D = vnorm(w), Q = vnorm(q);
+  const double k = kConeK * (D + RA) - RA;  // d radius / dt
+  const double ra = fabs(B.r) * (1.0 + 1e-5) + 1e-5 * (1.0 + 1e-6) * (Q + RA) + 1e-12;
+  const double slack = 1e-9 * (Q + D + RA + fabs(B.r));
+  double t = k > 0 ? 1.0 : 0.0;  // D == 0: f is linear in t
+  if (D > 0) {
+    const double qa = vdot(q, w) / D;                    // q along the axis
+    const double qn = vnorm(sub(q, vscale(w, qa / D)));  // and across it
+    const double kp = k / D;                             // (< kConeK; below -1: f rises, t = 0)
+    t = kp > -1.0 ? (qa + kp * qn / sqrt(1.0 - kp * kp)) / D : 0.0;
+    t = t > 0 ? (t < 1 ? t : 1.0) : 0.0;                 // (NaN: 0)
+  }
+  const v3 d = sub(q, vscale(w, t));
+  const double dl = vnorm(d);
+  const double f = dl - (RA + t * k);
+  const double df = -vdot(d, w) / dl - k;
+  const double low = f + fmin(-t * df, (1.0 - t) * df);
+  const double f1 = vnorm(sub(q, w)) - kConeK * (D + RA);
+  return low - slack > ra && f1 - slack > 1.41422 * ra;  // (a NaN: not clear)
+}
+}  // namespace
+
+bool cone_masks_apply(const FlatScene& fs) {
+  return fs.bvh.empty() && fs.spheres.size() <= 64 && fs.tris.size() <= 64;
+}
+
+void cone_rows(const FlatScene& fs, std::vector<unsigned long long>* rows) {
+  const size_t nl = fs.lights.size(), no = (size_t)fs.objects;
+  rows->assign(nl * no, ~0ull);
+  if (!cone_masks_apply(fs)) return;
+  double E = vnorm(arr(fs.cam_pos));
+  for (const DSphere& s : fs.spheres) E = fmax(E, vnorm(arr(s.c)) + fabs(s.r));
+  for (const DLight& l : fs.lights) E = fmax(E, vnorm(arr(l.pos)));
+  for (const DSphere& s : fs.spheres)  // (fmax drops a NaN)
+    if (!isfinite(s.c[0] + s.c[1] + s.c[2] + s.r)) return;
+  for (const DLight& l : fs.lights)
+    if (!isfinite(l.pos[0] + l.pos[1] + l.pos[2])) return;
+  if (!(E <= 1e15 && E >= 1e-100)) return;
+  for (size_t li = 0; li < nl; ++li)
+    for (const DSphere& A : fs.spheres) {  // (a cube's row stays full)
+      unsigned long long m = 0;
+      for (size_t b = 0; b < fs.spheres.size(); ++b)
+        if (&fs.spheres[b] == &A || !cone_clear(A, fs.spheres[b], arr(fs.lights[li].pos), E)) m |= 1ull << b;
+      (*rows)[li * no + (size_t)A.obj] = m;
+    }
+}
+
 // Go's Vec3 methods (internal/math/vector.go) on the host, for the frame
 namespace {
 struct V3 {

@@ -315,6 +315,7 @@ EXPORTED_SYMBOLS = [
     "rt_context_progressive_counts_async",
     "rt_context_progressive_state",
     "rt_adaptive_step",
+    "rt_scene_cone_rows",
 ]
 
 _lib = None
@@ -429,6 +430,7 @@ def lib():
         "rt_adaptive_step": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), i32, i32,
                                              i32, ctypes.POINTER(Adaptive), ctypes.POINTER(i32)]),
         "rt_camera_frame": (ctypes.c_int, [ctypes.POINTER(Camera), i32, i32, i32, ctypes.POINTER(ctypes.c_double)]),
+        "rt_scene_cone_rows": (ctypes.c_int, [ctypes.POINTER(SceneView), i32, ctypes.POINTER(ctypes.c_uint64), sz]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -996,6 +998,16 @@ def camera_frame(camera, model, width: int, height: int) -> np.ndarray:
     _check(lib().rt_camera_frame(ctypes.byref(camera), CAMERAS.get(model, model), width, height,
                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
     return out
+
+
+def cone_rows(scene: Scene, force_bvh: int = 0) -> np.ndarray:
+    """rt_scene_cone_rows: (num_lights, num_objects) uint64 -- per light and hittable, the spheres
+    (bit b: the scene's b-th sphere) a shadow cone of a hit on that hittable can hold (host only)."""
+    nl, no = int(scene.view.num_lights), int(scene.view.num_objects)
+    out = np.zeros(max(nl * no, 1), np.uint64)
+    _check(lib().rt_scene_cone_rows(ctypes.byref(scene.view), force_bvh,
+                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), out.size))
+    return out[: nl * no].reshape(nl, no)
 
 
 def render(scene: Scene, width: int, height: int, settings: Settings):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -284,6 +284,20 @@ int rt_validate(const rt_scene* scene, int32_t width, int32_t height, const rt_s
  * make in look-at mode.  The reference model reads position and aspect_ratio
  * only and checks nothing. */
 int rt_camera_frame(const rt_camera* cam, int32_t model, int32_t width, int32_t height, double out[12]);
+
+/* The shadow-cone rows of `scene` as rt_context_set_scene(scene, force_bvh)
+ * derives them (host only, no device): out[light * num_objects + hittable], one
+ * 64-bit mask each, num_lights * num_objects of them (capacity: the rows `out`
+ * holds; fewer is RT_E_INVALID).  Bit b of a row is CLEAR only when the b-th
+ * sphere of the scene (in hittable order, cubes not counted) provably stays
+ * clear of every shadow ray -- hard or soft -- that can leave a hit point on
+ * that hittable towards that light, so the shadow-cone test of such a hit
+ * never has to look at it.  The hit sphere's own bit is always set.  Every bit
+ * of a row is set (~0) where nothing is proven: the hittable is a cube, a
+ * centre, radius or light position of the scene is not finite, or the scene
+ * has no shadow-cone masks (a tree, more than 64 spheres, more than 64
+ * triangles). */
+int rt_scene_cone_rows(const rt_scene* scene, int32_t force_bvh, uint64_t* out, size_t capacity);
 
 /* ------------------------------------------ persistent multi-GPU renderer */
 
