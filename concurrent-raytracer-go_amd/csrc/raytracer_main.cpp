@@ -6,6 +6,7 @@
 //             [--sky default|white|sunset|night] [--camera reference|lookat]
 //             [--pass-samples N [--time-budget SECONDS] [--converge PIXELS]
 //              [--adaptive TOL[,PATIENCE[,MIN]]] [--count-map FILE]]
+//             [--orbit N[,DEGREES]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -24,7 +25,12 @@
 // benchmark_data.json records the samples actually rendered.  --adaptive
 //  stops every pixel on its own and the run once none is
 // active ("Pass k: n samples, a pixels active"); --count-map FILE writes the
-// per-pixel sample counts as a grey PNG, count * 255 / cap.
+// per-pixel sample counts as a grey PNG, count * 255 / cap.  --orbit N[,DEGREES]
+//  renders N views of the scene on one device, the scene's
+// camera turned about its up axis around its lookAt by DEGREES (360) in all
+// (rt_camera_orbit; --camera lookat makes the views differ in direction too),
+// as camera sequences of at most RT_MAX_FRAMES frames, and writes
+// <stem>_0000<ext> .. ; benchmark_data.json records "frames": N.
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -115,7 +121,7 @@ static void print_complete() {
 // SaveBenchmarkData (renderer.go:473-485): BenchmarkData JSON, 2-space indent,
 // next to the output (main.go:64-69)
 static void save_benchmark(const std::string& out_path, long long w, long long h, const rt_settings& st,
-                           const rt_stats& stats, double mean_samples = -1) {
+                           const rt_stats& stats, double mean_samples = -1, long long frames = -1) {
   std::string bench_path = dir_of(out_path) + "/benchmark_data.json";
   FILE* f = fopen(bench_path.c_str(), "wb");
   if (!f) {
@@ -128,6 +134,7 @@ static void save_benchmark(const std::string& out_path, long long w, long long h
     fprintf(f, "  \"samples\": %d,\n", st.samples);
     // (--adaptive: the mean samples per pixel actually rendered)
     if (mean_samples >= 0) fprintf(f, "  \"mean_samples_per_pixel\": %.17g,\n", mean_samples);
+    if (frames >= 0) fprintf(f, "  \"frames\": %lld,\n", frames);  // (--orbit)
     fprintf(f, "  \"max_depth\": %d,\n", st.max_depth);
     fprintf(f, "  \"num_workers\": %d,\n", st.num_workers);
     fprintf(f, "  \"objects\": %d,\n", stats.objects);
@@ -261,8 +268,77 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
   return RT_OK;
 }
 
+// --orbit: n views of rt_camera_orbit of the scene's camera through
+// rt_context_render_cameras_async on device 0, RT_MAX_FRAMES at a time; each
+// launch's images go to save(first frame, frames, their RGBA8 images, w*h*4
+// bytes each), which returns false to stop (RT_E_IO); fills stats.
+template <class Save>
+static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int n, double degrees,
+                        Save save, rt_stats* stats) {
+  std::vector<rt_camera> cams((size_t)n);
+  int rc = rt_camera_orbit(&scene->camera, n, degrees, cams.data());
+  if (rc != RT_OK) return rc;
+  const auto t_new = std::chrono::steady_clock::now();
+  rt_context* ctx = nullptr;
+  if (rt_context_create(0, &ctx) != RT_OK) return RT_E_DEVICE;
+  stats->create_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_new).count();
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t npix = (size_t)w * (size_t)h;
+  rc = rt_context_set_scene(ctx, scene, 0);
+  stats->scene_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  auto hip_ok = [&](hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    fprintf(stderr, "%s failed: %s\n", what, hipGetErrorString(e));
+    rc = RT_E_DEVICE;
+    return false;
+  };
+  const int per = std::min(n, RT_MAX_FRAMES);
+  std::vector<uint8_t> rgba((size_t)per * npix * 4);
+  float* d_lin = nullptr;
+  uint8_t* d_img = nullptr;
+  if (rc == RT_OK && hip_ok(hipMalloc((void**)&d_lin, (size_t)per * npix * 12), "hipMalloc"))
+    hip_ok(hipMalloc((void**)&d_img, (size_t)per * npix * 4), "hipMalloc");
+  double kernel_s = 0, save_s = 0;
+  for (int f0 = 0; rc == RT_OK && f0 < n; f0 += per) {
+    const int m = std::min(per, n - f0);
+    float* lin[RT_MAX_FRAMES];
+    uint8_t* img[RT_MAX_FRAMES];
+    for (int f = 0; f < m; ++f) {
+      lin[f] = d_lin + (size_t)f * npix * 3;
+      img[f] = d_img + (size_t)f * npix * 4;
+    }
+    rc = rt_context_render_cameras_async(ctx, w, h, &st, m, cams.data() + f0, nullptr, 0, 1, RT_LAYOUT_IMAGE, lin, img,
+                                         nullptr);
+    if (rc != RT_OK) break;
+    if (!hip_ok(hipMemcpy(rgba.data(), d_img, (size_t)m * npix * 4, hipMemcpyDeviceToHost), "hipMemcpy")) break;
+    double ks = 0;
+    if (rt_context_last_kernel_seconds(ctx, &ks) == RT_OK) kernel_s += ks;
+    const auto t_save = std::chrono::steady_clock::now();  // (writing the files is not render time)
+    if (!save(f0, m, rgba.data())) rc = RT_E_IO;
+    save_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_save).count();
+  }
+  const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
+  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - save_s;
+  for (void* p : {(void*)d_lin, (void*)d_img})
+    if (p) (void)hipFree(p);
+  rt_context_destroy(ctx);
+  if (rc != RT_OK) {
+    if (!err.empty()) fprintf(stderr, "%s\n", err.c_str());
+    return rc;
+  }
+  stats->render_seconds = secs;
+  stats->kernel_seconds = kernel_s;
+  stats->objects = scene->num_objects;
+  stats->lights = scene->num_lights;
+  stats->rays_per_second = (double)npix * st.samples * n / secs;
+  stats->pixels_per_second = (double)npix * n / secs;
+  return RT_OK;
+}
+
 int main(int argc, char** argv) {
   std::vector<std::string> args;
+  long long orbit_n = 0;       // --orbit N[,DEGREES] (0: one render)
+  double orbit_deg = 360.0;
   double watchdog_s = 0;  // --watchdog (0: no bound, as Go's Render)
   long long pass_samples = 0, converge = -1;  // --pass-samples (0: one render), --converge (-1: off)
   double budget_s = -1;                       // --time-budget (-1: off)
@@ -351,6 +427,22 @@ int main(int argc, char** argv) {
       adapt.patience = (int32_t)f[1];
       adapt.min_samples = (int32_t)f[2];
       adaptive_on = true;
+    } else if (a == "--orbit") {  // N views around the scene's lookAt
+      const std::string x = need("--orbit");
+      const size_t comma = x.find(',');
+      bool ok = parse_int(x.substr(0, comma).c_str(), &v) && v >= 1 && v <= 9999;  // (four digits name a file)
+      if (ok && comma != std::string::npos) {
+        char* end = nullptr;
+        errno = 0;
+        orbit_deg = strtod(x.c_str() + comma + 1, &end);
+        ok = end && end != x.c_str() + comma + 1 && *end == 0 && errno == 0 && orbit_deg == orbit_deg &&
+             orbit_deg - orbit_deg == 0;  // (finite)
+      }
+      if (!ok) {
+        fprintf(stderr, "invalid --orbit %s (N[,DEGREES]: N in 1..9999)\n", x.c_str());
+        return 2;
+      }
+      orbit_n = v;
     } else if (a == "--count-map") {  // --adaptive: the per-pixel sample counts as a grey PNG
       count_map = need("--count-map");
     } else if (a == "--sky") {  // opt-in sky on miss (atmosphere.go presets); default: black
@@ -375,6 +467,10 @@ int main(int argc, char** argv) {
     } else {
       args.push_back(a);
     }
+  }
+  if (orbit_n > 0 && (pass_samples > 0 || adaptive_on || st.num_devices > 1)) {
+    fprintf(stderr, "--orbit renders whole frames on one device: not with --pass-samples, --adaptive or --devices > 1\n");
+    return 2;
   }
   if (pass_samples > 0 && st.num_devices > 1) {
     fprintf(stderr, "--pass-samples renders on one device (--devices %d)\n", st.num_devices);
@@ -462,6 +558,47 @@ int main(int argc, char** argv) {
       return 1;
     }
     save_benchmark(out_path, w, h, st, stats);
+    rt_scene_free(sb);
+    return 0;
+  }
+  if (orbit_n > 0) {
+    printf("Rendering at %lldx%lld resolution...\n", w, h);
+    fflush(stdout);
+    rt_scene_print_hittables(sb);
+    const size_t npix = (size_t)w * (size_t)h;
+    rt_stats stats;
+    memset(&stats, 0, sizeof stats);
+    std::string out_path = output_file;
+    if (ext_of(out_path).empty()) out_path += ".png";
+    const std::string ext = ext_of(out_path), stem = out_path.substr(0, out_path.size() - ext.size());
+    bool save_failed = false;
+    // (each launch's frames are written as they arrive: the host holds one launch's images)
+    auto save = [&](int f0, int m, const uint8_t* imgs) {
+      for (int f = 0; f < m; ++f) {
+        char num[32];
+        snprintf(num, sizeof num, "_%04d", f0 + f);
+        const std::string fp = stem + num + ext;
+        printf("Saving to: %s\n", fp.c_str());
+        fflush(stdout);
+        const uint8_t* img = imgs + (size_t)f * npix * 4;
+        const int rc = ext == ".ppm" ? rt_write_ppm(fp.c_str(), img, (int32_t)w, (int32_t)h)
+                                     : rt_write_png(fp.c_str(), img, (int32_t)w, (int32_t)h);
+        if (rc != RT_OK) {
+          printf("Error saving image: %s\n", rt_last_error());
+          save_failed = true;
+          return false;
+        }
+      }
+      return true;
+    };
+    if (rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK ||
+        render_orbit(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)orbit_n, orbit_deg, save, &stats) != RT_OK) {
+      if (!save_failed) fprintf(stderr, "render failed: %s\n", rt_last_error());
+      rt_scene_free(sb);
+      return save_failed ? 1 : 2;
+    }
+    print_complete();
+    save_benchmark(out_path, w, h, st, stats, -1, orbit_n);
     rt_scene_free(sb);
     return 0;
   }

@@ -69,6 +69,9 @@ struct rt_context {
     // adaptive sampling: [totals, 256 B][count][streak][active][rgba], one
     // word per local pixel each
     DevBuf adapt;
+    // a camera sequence's CamFrames: kMaxFrames rows, the
+    // table of the set last rendered (seq_cams)
+    DevBuf cams;
     DevBuf* begin() { return &scene; }
     DevBuf* end() { return begin() + sizeof(DevBufs) / sizeof(DevBuf); }
   } d;
@@ -88,7 +91,7 @@ struct rt_context {
   unsigned long long* dbg = nullptr;
   // the work schedule (rt_schedule.hip), cached per (scene, W, H, rank, world, settings)
   uint64_t scene_gen = 0;
-  int64_t order_key[15] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int64_t order_key[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   int32_t num_blocks = 0;
   int32_t nsplit = 0;        // split pixels of the current schedule
   int32_t split_frames = 0;  // frames whose copies of the split rows are laid out in d.split
@@ -151,6 +154,15 @@ struct rt_context {
   int64_t adapt_inimg = 0, adapt_active = 0, adapt_sum = 0, adapt_gen = 0;
   int64_t prog_adds = 0;
   bool adapt_pending = false;  // an add's totals are on their way to h_adapt
+  // camera sequences.  The scene's camera reaches the
+  // schedule key through scene_gen; a camera given with a render reaches it
+  // through a generation of this counter: a sequence takes a new one when its
+  // set of frames differs from the last sequence's (seq_cams, seq_n: the set in
+  // d.cams, keyed seq_gen), a frame rendered alone with a camera of its own
+  // takes a new one every time (keyed by its negative).  0 keys the scene's view.
+  int64_t cam_gen = 0, seq_gen = 0;
+  int32_t seq_n = 0;
+  rtgo::CamTable seq_cams{};
 };
 
 namespace rtgo {
@@ -248,8 +260,10 @@ inline int leave_stream(rt_context* c, hipStream_t s) {
 
 // The launch parameters of a render of (w, h, st) by `rank` of `world`
 // (outputs, counters and schedule are filled in by the caller).
+// cam: the frame to shoot from instead of the scene's camera (a camera
+// sequence's frame rendered alone; validated by its caller).
 inline void base_params(const rt_context* c, int w, int h, const rt_settings* st, int rank, int world, int layout,
-                        KParams* out) {
+                        KParams* out, const CamFrame* cam = nullptr) {
   const FlatScene& f = c->flat;
   KParams& p = *out;
   memset(&p, 0, sizeof p);
@@ -263,7 +277,8 @@ inline void base_params(const rt_context* c, int w, int h, const rt_settings* st
   p.sky = st->sky != RT_SKY_NONE ? c->d_sky + (st->sky - 1) : nullptr;
   p.dbg = c->dbg;
   // (the entry points have validated st and the camera: check_frame)
-  (void)camera_frame(f.camera, st->camera, w, h, &p.cf);
+  if (cam) p.cf = *cam;
+  else (void)camera_frame(f.camera, st->camera, w, h, &p.cf);
   p.seed_key = rt_rng_seed_key(st->seed);
   p.ns = (int32_t)f.spheres.size();
   p.nt = (int32_t)f.tris.size();
@@ -285,6 +300,8 @@ inline void base_params(const rt_context* c, int w, int h, const rt_settings* st
   p.stage_src = c->d.scene.p;
   p.stage_bytes = c->tun.stage ? c->stage_bytes : 0;
   p.cone_rows_off = p.stage_bytes > 0 ? c->cone_rows_off : 0;
+  // (the rows' margins are derived for rays from within the scene's extent)
+  if (cam && p.cone_rows_off && !cone_rows_hold(f, cam->o)) p.cone_rows_off = 0;
   p.stack_off = (p.stage_bytes + 15) & ~15;
   p.stack_depth = std::max(1, f.bvh_depth);
 }
@@ -308,8 +325,17 @@ SchedParams sched_params(rt_context* c, const KParams& p, const rt_settings* st,
                          const int32_t* d_tiles, bool masks, bool frustum, double block_work, int bigP, void* scratch,
                          unsigned long long* d_masks, float* d_cost);
 int run_pilot(const rt_context* c, const KParams& p, SchedParams* sp, char* buf, hipStream_t s);
+// A render whose camera is not the scene's: the generation
+// that keys its schedule (rt_context::cam_gen; 0: the scene's view) and, for a
+// sequence, its n frames -- the schedule's pixel masks and live-pixel list
+// are then the union over them (the table is in d.cams when it is built).
+struct CamKey {
+  int64_t gen = 0;
+  const CamFrame* frames = nullptr;
+  int n = 0;
+};
 int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream_t s, int frames = 1,
-                     const uint32_t* active = nullptr, int64_t active_gen = 0);
+                     const uint32_t* active = nullptr, int64_t active_gen = 0, const CamKey& cam = CamKey());
 // The sample passes of one frame or of one add of a progression (between
 // enter_stream and leave_stream): samples [first, first + n) of spp_total.
 struct PassOpts {
@@ -324,6 +350,7 @@ struct PassOpts {
   // an adaptive add's active flags and their generation (prepare_schedule)
   const uint32_t* active = nullptr;
   int64_t active_gen = 0;
+  CamKey cam;  // a frame with a camera of its own (its p.cf is base_params's override)
 };
 int render_passes(rt_context* c, KParams* p, const rt_settings* st, hipStream_t s, const PassOpts& o);
 

@@ -77,6 +77,14 @@ void flatten_scene(const rt_scene& s, FlatScene* out);
 // under that light.  Full rows (~0) without shadow-cone masks (cone_masks_apply:
 // a tree, or more than 64 spheres or triangles), for cubes and non-finite scenes.
 bool cone_masks_apply(const FlatScene& fs);
+// The extent E those rows' margins are derived for (centres + radii, lights,
+// the scene's camera): a camera ray from farther out than the proof allows
+// (cone_rows_hold) must not use the rows.
+double cone_extent(const FlatScene& fs);
+// Do the rows hold for camera rays that start at `origin`?  The hit point's
+// error bound 2e-7 E (scene_flat.cpp) covers sqrt(1e-15) |o - c| for every
+// |o| <= 2 E: |o - c| <= 3 E gives 9.5e-8 E.
+bool cone_rows_hold(const FlatScene& fs, const double origin[3]);
 void cone_rows(const FlatScene& fs, std::vector<unsigned long long>* rows);
 // Binned-SAH BVH over out->spheres and out->boxes, a cube being one primitive
 // (reorders both arrays; the triangles stay).  Leaves hold one kind.
@@ -154,6 +162,14 @@ size_t sched_scratch_bytes(int local);
 void sched_layout(void* scratch, int local, SchedParams* p);
 // masks + pilot blocks (zeroes the class counters first)
 int sched_launch_pixels(const SchedParams& p, void* stream);
+// The same for a camera sequence: a pixel's masks are the OR
+// over the ncams cameras of its masks under camera k -- d_cams[k] within
+// d_cam_masks[(k * p.local + lt) * 2 ..], camera k's own tile masks -- so the
+// live-pixel list built from them is the union of the cameras' live pixels.
+// p.tile_masks: the OR of the cameras' tile masks (black tiles, the pilot).
+// A kernel of its own: the schedulers of every other render keep their code.
+int sched_launch_pixels_seq(const SchedParams& p, const CamFrame* d_cams, int ncams,
+                            const unsigned long long* d_cam_masks, void* stream);
 // write = false: estimates, pass 1 (class counts, split count), scan;
 // write = true: pass 2 (the records)
 int sched_launch_blocks(const SchedParams& p, bool write, void* stream);
@@ -359,17 +375,28 @@ struct StreamParams {
   // a progression's add: each local pixel's running sum
   // (KParams::acc layout), which the resolve continues and stores back; null: from +0
   double* acc;
+  // a camera sequence: the CamFrame of each frame of KParams::frame_* (device memory,
+  // kMaxFrames rows; 32 of them do not fit the 4-KB argument block beside KParams), which frame fl of the
+  // launch shoots from instead of KParams::cf; null: every frame shoots from KParams::cf.  Last, so that
+  // no offset of the kernels' argument moves.
+  const CamFrame* cams;
 };
 struct StreamKArgs {           // the kernels' one argument: KParams at offset 0 (rt_kernel.hip fresh())
   KParams k;
   StreamParams s;
 };
 // The launch's stream kernel (stream_kernel_of: generic or spheres-only, each
-// with its sample_base twin) on `wgs` one-wave workgroups, then
-// resolve_rows_kernel; the cursor is zeroed first.
+// with its sample_base twin and its camera-sequence build, sp.cams) on `wgs`
+// one-wave workgroups, then resolve_rows_kernel; the cursor is zeroed first.
 int launch_stream(const KParams& p, const StreamParams& sp, int wgs, void* stream);
-constexpr int kStreamKernels = 4;
-int stream_kernel_of(const KParams& p);
+constexpr int kStreamKernels = 6;
+int stream_kernel_of(const KParams& p, bool cams = false);
+// Writes the n CamFrames (passed by value, in the launch's arguments: no host
+// buffer outlives the call) to d_cams on the stream.
+struct CamTable {
+  CamFrame f[kMaxFrames];
+};
+int launch_cam_upload(const CamTable& t, int n, CamFrame* d_cams, void* stream);
 // resident one-wave workgroups of stream kernel `kernel` with `shmem` bytes of
 // dynamic LDS on `device` (the runtime's occupancy x CUs; 0: no answer)
 int stream_wave_slots(int device, int kernel, size_t shmem);

@@ -1830,8 +1830,12 @@ __device__ __forceinline__ uint2 stream_claim_chunk() {
 }
 // ... and the set-up of queue entry e: its camera ray and soft-shadow key
 // exactly as the block kernel's refill builds them (kBase: the frame's sample
-// sample_base + s, a progression's add); returns its row
-template <bool kBase>
+// sample_base + s, a progression's add); returns its row.
+// kCams (a camera sequence): the entry's frame shoots from its
+// own CamFrame, row frame0 + fl of the launch's table in device memory (one
+// load per lane: with order 1 neighbouring lanes hold different frames); only
+// here, at entry set-up -- nothing after the camera ray reads a camera.
+template <bool kBase, bool kCams>
 __device__ __forceinline__ int stream_entry(unsigned e, rt_rng& rng, d3& o, d3& d, uint64_t (&skey)[64]) {
   const SArg sk = sfresh();
   const unsigned spp = (unsigned)sk->k.spp, nlive = (unsigned)sk->s.nlive;
@@ -1851,8 +1855,13 @@ __device__ __forceinline__ int stream_entry(unsigned e, rt_rng& rng, d3& o, d3& 
   const uint64_t fkey = sk->k.frame_key[sk->s.frame0 + (int)fl];
   Counters nc;
   const unsigned fs = kBase ? (unsigned)sk->k.sample_base + s : s;
-  camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, sk->k.cf), sk->k.cf,
-                      it.x, it.y, (int)fs, rng, o, d, nc);
+  if constexpr (kCams) {
+    const CamFrame& cf = sk->s.cams[sk->s.frame0 + (int)fl];
+    camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, cf), cf, it.x, it.y, (int)fs, rng, o, d, nc);
+  } else {
+    camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, sk->k.cf), sk->k.cf,
+                        it.x, it.y, (int)fs, rng, o, d, nc);
+  }
   skey[lane_now()] = rt_soft_key(fkey, (uint32_t)it.y * (uint32_t)sk->k.W + (uint32_t)it.x, (uint32_t)fs);
   return (int)((fl * spp + s) * nlive + i);
 }
@@ -1916,6 +1925,7 @@ struct BodySwitches {  // (the defaults: a variant names only what it turns on)
   static constexpr bool stream = false;  // drains the launch-wide entry queue
   static constexpr bool base = false;    // (stream) entry samples start at sample_base
   static constexpr bool sph = false;     // (stream) the scene is spheres alone
+  static constexpr bool cams = false;    // (stream) every frame of the launch has a camera of its own
   static constexpr bool mix = false;     // the BVH has leaves of cubes (bvh.cpp; KParams.use_bvh == 2)
 };
 template <bool kCount, bool kStage, bool kPilot, bool kSky>
@@ -1941,10 +1951,17 @@ struct StreamSphBody : StreamBody {  // render_stream_sph_kernel
 struct StreamSphBaseBody : StreamSphBody {  // render_stream_sph_base_kernel
   static constexpr bool base = true;
 };
+struct StreamCamsBody : StreamBody {  // render_stream_cams_kernel
+  static constexpr bool cams = true;
+};
+struct StreamSphCamsBody : StreamSphBody {  // render_stream_sph_cams_kernel
+  static constexpr bool cams = true;
+};
 template <class V>
 constexpr bool body_variant_ok() {
   static_assert(!V::stream || (V::stage && !V::count && !V::pilot && !V::sky && !V::tail), "the stream kernel is the staged product body");
   static_assert(!V::sph || V::stream, "spheres-only is a build of the stream kernel");
+  static_assert(!V::cams || (V::stream && !V::base), "a camera sequence is a streamed launch, never a progression's add");
   static_assert(!V::mix || (!V::stage && !V::stream && !V::tail), "a BVH scene is not staged");
   return true;
 }
@@ -1953,7 +1970,7 @@ template <class V>
 __device__ __forceinline__ void render_body(const KParams& pk) {
   static_assert(body_variant_ok<V>(), "");
   constexpr bool kCount = V::count, kStage = V::stage, kPilot = V::pilot, kSky = V::sky, kStream = V::stream,
-                 kBase = V::base, kSph = V::sph, kMix = V::mix;
+                 kBase = V::base, kSph = V::sph, kMix = V::mix, kCams = V::cams;
   typedef typename Kind<kSph>::C CandK;
   typedef typename Kind<kSph>::H HitK;
   __shared__ uint32_t hbits[kStream ? 1 : kMaxBlockSamples / 32];  // hit samples of the block
@@ -2233,7 +2250,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             }
             const unsigned e = qbeg + (unsigned)lanes_below(fm);
             if (!alive && e < qend) {
-              entry = stream_entry<kBase>(e, rng, o, d, skey);
+              entry = stream_entry<kBase, kCams>(e, rng, o, d, skey);
               set_path_T(mk(1, 1, 1));
               if constexpr (kSph) {
                 // (the zero made here: held in a register pair from the
@@ -2789,6 +2806,15 @@ __global__ __launch_bounds__(64, RT_STREAM_SPH_WAVES) void render_stream_sph_ker
 __global__ __launch_bounds__(64, RT_STREAM_SPH_WAVES) void render_stream_sph_base_kernel(const StreamKArgs a) {
   render_body<StreamSphBaseBody>(a.k);
 }
+// The two of a camera sequence (kCams): frame fl of the launch
+// shoots from StreamParams::cams[frame0 + fl].  No kBase twins: a progression
+// has one camera.
+__global__ __launch_bounds__(64, RT_WAVES_PER_SIMD) void render_stream_cams_kernel(const StreamKArgs a) {
+  render_body<StreamCamsBody>(a.k);
+}
+__global__ __launch_bounds__(64, RT_STREAM_SPH_WAVES) void render_stream_sph_cams_kernel(const StreamKArgs a) {
+  render_body<StreamSphCamsBody>(a.k);
+}
 // After it on the same stream: one lane per pixel of the rank's tiles, per
 // frame of the launch (blockIdx.y).  Lane t writes local pixel t black when it
 // is not live (what the block kernel's epilogue writes for it: a sum of +0),
@@ -2837,17 +2863,24 @@ __global__ __launch_bounds__(256) void resolve_rows_kernel(const StreamKArgs a) 
 }
 
 // The stream kernel of a launch (kStreamKernels of them): bit 0 the kBase
-// twin, bit 1 the spheres-only build.
+// twin, bit 1 the spheres-only build; 4 and 5: a camera sequence's generic and
+// spheres-only kernels.
 typedef void (*StreamKernel)(const StreamKArgs);
 static StreamKernel stream_kernel_fn(int kernel) {
   switch (kernel) {
     case 0: return render_stream_kernel;
     case 1: return render_stream_base_kernel;
     case 2: return render_stream_sph_kernel;
-    default: return render_stream_sph_base_kernel;
+    case 3: return render_stream_sph_base_kernel;
+    case 4: return render_stream_cams_kernel;
+    default: return render_stream_sph_cams_kernel;
   }
 }
-int stream_kernel_of(const KParams& p) { return (p.sample_base != 0 ? 1 : 0) | (p.nt == 0 && p.nb == 0 ? 2 : 0); }
+int stream_kernel_of(const KParams& p, bool cams) {
+  const bool sph = p.nt == 0 && p.nb == 0;
+  if (cams) return sph ? 5 : 4;
+  return (p.sample_base != 0 ? 1 : 0) | (sph ? 2 : 0);
+}
 
 // Resident one-wave workgroups of that kernel on `device` (the current one)
 // with `shmem` bytes of dynamic LDS: what the runtime reports per CU for the
@@ -2882,11 +2915,13 @@ int launch_stream(const KParams& pin, const StreamParams& sp, int wgs, void* str
   single_frame_entry(p);
   p.tail = nullptr;
   if (p.stage_bytes <= 0 || p.use_bvh || wgs <= 0 || sp.frames <= 0 || sp.npix <= 0) return (int)hipErrorInvalidValue;
+  // (a sequence's table holds a frame per entry of frame_*; its kernels have no sample_base twin)
+  if (sp.cams && (p.sample_base != 0 || sp.frame0 < 0 || sp.frame0 + sp.frames > kMaxFrames)) return (int)hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(sp.cursor, 0, sizeof(unsigned int), st);
   if (e != hipSuccess) return (int)e;
   // (a scene without triangles and cubes -- every scene the auto rule streams
   // -- takes the spheres-only build; triangles streamed by force the generic one)
-  hipLaunchKernelGGL(stream_kernel_fn(stream_kernel_of(p)), dim3(wgs), dim3(64), render_shmem(p), st, a);
+  hipLaunchKernelGGL(stream_kernel_fn(stream_kernel_of(p, sp.cams != nullptr)), dim3(wgs), dim3(64), render_shmem(p), st, a);
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(resolve_rows_kernel, dim3((unsigned)((sp.npix + 255) / 256), (unsigned)sp.frames), dim3(256), 0, st, a);
@@ -3129,6 +3164,24 @@ int launch_download(const void* d_src, void* h_dst_mapped, size_t bytes, void* s
   const unsigned grid = (unsigned)((n16 + 255) / 256 < 2048 ? (n16 + 255) / 256 : 2048);
   hipLaunchKernelGGL(download_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4*)d_src,
                      (uint4*)h_dst_mapped, n16);
+  return (int)hipGetLastError();
+}
+
+// A camera sequence's CamFrames from the launch's own arguments to the table
+// the stream kernels read: the runtime copies the arguments
+// when the launch is enqueued, so nothing of the caller's is read later and no
+// staging buffer has to outlive the call.  One 8-byte word per lane.
+__global__ __launch_bounds__(64) void cam_upload_kernel(const CamTable t, int words, uint64_t* __restrict__ dst) {
+  static_assert(sizeof(CamFrame) % 8 == 0 && sizeof(CamTable) + 16 <= 4096, "the table travels as a kernel argument");
+  const uint64_t* src = reinterpret_cast<const uint64_t*>(&t);
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i < words) dst[i] = src[i];
+}
+int launch_cam_upload(const CamTable& t, int n, CamFrame* d_cams, void* stream) {
+  if (n < 1 || n > kMaxFrames || !d_cams) return (int)hipErrorInvalidValue;
+  const int words = n * (int)(sizeof(CamFrame) / 8);
+  hipLaunchKernelGGL(cam_upload_kernel, dim3((unsigned)((words + 63) / 64)), dim3(64), 0, (hipStream_t)stream, t, words,
+                     reinterpret_cast<uint64_t*>(d_cams));
   return (int)hipGetLastError();
 }
 

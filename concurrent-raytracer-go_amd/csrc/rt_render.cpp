@@ -1,6 +1,8 @@
 // rt_render.cpp — a frame's launch sequence: the work schedule, the tail
-// helpers, the streamed launch, the sample passes, and the single-frame and
-// batched render entry points (include/rt_api.h).
+// helpers, the streamed launch, the sample passes, and the single-frame,
+// batched and camera-sequence render entry points (include/rt_api.h).
+#include <math.h>
+
 #include "rt_context.h"
 
 namespace rtgo {
@@ -208,8 +210,12 @@ static bool stream_wanted(const rt_context* c, const KParams& p, const rt_settin
 // active (an adaptive progression's add): the per-pixel active
 // flags folded into the pixels' primary masks, the schedule keyed by the
 // active set's generation `active_gen`; null: an ordinary schedule.
+// cam: a render whose camera is not the scene's is keyed by
+// cam.gen; a sequence (cam.n frames, their table in d.cams) gets the union of
+// its cameras' pixel masks, so its live-pixel list holds every pixel that any
+// frame's rays may hit.
 int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream_t s, int frames,
-                     const uint32_t* active, int64_t active_gen) {
+                     const uint32_t* active, int64_t active_gen, const CamKey& cam) {
   const FlatScene& f = c->flat;
   const int w = p->W, h = p->H, rank = p->rank, world = p->world;
   const rt_tuning& tn = c->tun;
@@ -223,13 +229,14 @@ int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream
   const bool sky = st->sky != RT_SKY_NONE;
   const bool frustum = tn.frustum != 0 && !sky;
   const bool part = use_partition(c, w, h, world);
-  const int64_t key[15] = {(int64_t)c->scene_gen, w, h, rank, world, st->samples, st->max_depth,
+  const int64_t key[16] = {(int64_t)c->scene_gen, w, h, rank, world, st->samples, st->max_depth,
                            st->recursive_reflections, st->soft_shadows, bigP, (int64_t)(block_work * 16),
                            (pilot ? 1 + tn.pilot_depth : 0) | (int64_t)tn.split_samples << 16,
                            (frustum ? 1 : 0) | (sky ? 2 : 0) | (tn.measure ? 4 : 0) | (want_live ? 8 : 0) | (st->camera ? 16 : 0) |
                                (int64_t)tn.split_depth << 8,
                            part ? (int64_t)c->part->id : 0,
-                           active ? active_gen + 1 : 0};
+                           active ? active_gen + 1 : 0,
+                           cam.gen};
   // the pixels' primary masks: the scene's candidate masks where they apply; an
   // adaptive add without them (or without primary culling) gets masks of its
   // own that hold every primitive and only carry the active flags
@@ -262,6 +269,17 @@ int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream
         for (int lt = 0; lt < local; ++lt) {
           c->masks_host[2 * lt] = ms;
           c->masks_host[2 * lt + 1] = mt;
+        }
+      } else if (masks && cam.n > 0) {
+        // a sequence: [the OR of the cameras' tile masks][camera 0's][camera 1's] ...
+        c->masks_host.assign((size_t)local * 2 * (size_t)(cam.n + 1), 0ull);
+        std::vector<unsigned long long> one;
+        for (int k = 0; k < cam.n; ++k) {
+          tile_primary_masks(f, cam.frames[k], w, h, tiles, &one);
+          for (size_t i = 0; i < (size_t)local * 2; ++i) {
+            c->masks_host[i] |= one[i];
+            c->masks_host[(size_t)local * 2 * (size_t)(k + 1) + i] = one[i];
+          }
         }
       } else if (masks) {
         tile_primary_masks(f, p->cf, w, h, tiles, &c->masks_host);
@@ -308,7 +326,9 @@ int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream
                                     bigP, c->d.sched.p, c->d_masks, d_cost);
       sp.active = active;
       sp.own_masks = own_masks ? 1 : 0;
-      rc = launched(sched_launch_pixels(sp, s));
+      rc = launched(cam.n > 0 ? sched_launch_pixels_seq(sp, c->d.cams.as<const CamFrame>(), cam.n,
+                                                        masks ? c->d_masks + (size_t)local * 2 : nullptr, s)
+                              : sched_launch_pixels(sp, s));
       if (rc) return fail_synced(rc);
       if (remeasured) {  // every sample's path of the last frame (the measuring render)
         sp.work_max = c->d.meas.as<const unsigned int>();
@@ -392,8 +412,9 @@ int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream
 // frames take 573 MB).  *streamed stays false when the launch is not eligible
 // or not even two of its frames (the frame of a one-frame launch) fit: it then
 // takes the block kernel as before.
+// cams (a camera sequence): the frames' CamFrame table.
 static int render_stream(rt_context* c, const KParams& p, const rt_settings* st, int nframes, int key_frames,
-                         hipStream_t s, bool* streamed) {
+                         hipStream_t s, bool* streamed, const CamFrame* cams = nullptr) {
   *streamed = false;
   const bool prog = p.acc_mode == kAccProgressive && nframes == 1;
   if (!stream_wanted(c, p, st, key_frames) || c->nlive < 0 || p.counts || p.work_max || (p.acc_mode != 0 && !prog) ||
@@ -408,7 +429,7 @@ static int render_stream(rt_context* c, const KParams& p, const rt_settings* st,
   if (group < std::min(nframes, 2)) return RT_OK;
   // the grid: the resident waves of the kernel this launch takes (cached per
   // kernel; a new scene can change its dynamic LDS)
-  const int kid = stream_kernel_of(p);
+  const int kid = stream_kernel_of(p, cams != nullptr);
   const size_t shmem = render_shmem(p);
   if (c->wave_slots[kid] <= 0 || c->wave_shmem[kid] != shmem) {
     c->wave_slots[kid] = stream_wave_slots(c->device, kid, shmem);
@@ -434,6 +455,7 @@ static int render_stream(rt_context* c, const KParams& p, const rt_settings* st,
   sp.chunk = tn.stream_chunk > 0 ? tn.stream_chunk : 512;
   sp.order = tn.stream_order;
   sp.acc = prog ? p.acc : nullptr;  // (the resolve continues the progression's sums)
+  sp.cams = cams;
   for (int f0 = 0; f0 < nframes; f0 += group) {
     sp.frame0 = f0;
     sp.frames = std::min(group, nframes - f0);
@@ -500,7 +522,7 @@ int render_passes(rt_context* c, KParams* pp, const rt_settings* st, hipStream_t
     p.acc_mode = o.keep ? (1 | (last ? 4 : 2)) : ((pass > 0 ? 1 : 0) | (last ? 0 : 2));
     if (!wf) {
       // (keyed by the pass's sample count, not by sample_base: equal adds share a schedule)
-      rc = prepare_schedule(c, &p, &ps, s, o.key_frames, o.active, o.active_gen);
+      rc = prepare_schedule(c, &p, &ps, s, o.key_frames, o.active, o.active_gen, o.cam);
       if (rc) return rc;
     }
     p.num_wgs = p.num_blocks;
@@ -564,14 +586,19 @@ using namespace rtgo;
 // one of n frames that rt_context_render_frames_async renders one at a time
 // (a measuring frame): the schedule key then stays the batched launch's, so
 // the measured re-cut is the one the next batched launch reuses.
+// cam: the frame shoots from this CamFrame instead of the scene's camera (a
+// camera sequence's frame rendered alone): the override goes
+// into base_params, the flattened scene keeps its camera, and the frame's
+// schedule is keyed by a generation of its own -- never shared, rebuilt for
+// every such frame.
 static int render_one(rt_context* c, int32_t w, int32_t h, const rt_settings* st, int32_t rank, int32_t world,
                       int32_t layout, float* d_linear, uint8_t* d_rgba, void* stream, rt_counts* counts,
-                      int key_frames) {
+                      int key_frames, const CamFrame* cam = nullptr) {
   int rc = check_frame_args(c, w, h, st, rank, world, layout);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
   KParams p;
-  base_params(c, w, h, st, rank, world, layout, &p);
+  base_params(c, w, h, st, rank, world, layout, &p, cam);
   p.out_linear = d_linear;
   p.out_rgba = d_rgba;
   if (counts && (rc = grow(c, &c->d.counts, kCountSlots * sizeof(unsigned long long)))) return rc;
@@ -583,6 +610,7 @@ static int render_one(rt_context* c, int32_t w, int32_t h, const rt_settings* st
   o.key_frames = key_frames;
   o.counts = counts;
   o.may_measure = true;
+  if (cam) o.cam.gen = -(++c->cam_gen);
   rc = enter_stream(c, s);
   if (!rc) rc = render_passes(c, &p, st, s, o);
   return rc ? rc : leave_stream(c, s);
@@ -649,6 +677,131 @@ int rt_context_render_frames_async(rt_context* c, int32_t w, int32_t h, const rt
   c->stats.launches += 1;
   c->stats.batched_launches += 1;
   return leave_stream(c, s);
+}
+
+// The frames of one launch, each with a camera of its own (include/rt_api.h,
+// DESIGN.md §4.11).  Where a batched launch of nframes frames would stream
+// (stream_wanted), the frames are ONE streamed launch on one schedule whose
+// live-pixel list is the union over the cameras; everywhere else -- one frame,
+// the wavefront path, sample passes, a sky, a measuring schedule, tail
+// helpers, triangles under the auto rule, a row budget that holds fewer than
+// two frames -- they render frame by frame, each with its camera as an
+// override of base_params: correct and slow, a new schedule per frame.
+int rt_context_render_cameras_async(rt_context* c, int32_t w, int32_t h, const rt_settings* st, int32_t nframes,
+                                    const rt_camera* cameras, const uint64_t* seeds, int32_t rank, int32_t world,
+                                    int32_t layout, float* const* d_linear, uint8_t* const* d_rgba, void* stream) {
+  if (c && c->have_scene && (nframes < 1 || nframes > RT_MAX_FRAMES || !cameras || !d_linear)) {
+    set_error("rt_context_render_cameras_async: nframes must be in [1, RT_MAX_FRAMES] with cameras and d_linear given");
+    return RT_E_INVALID;
+  }
+  int rc = check_frame_args(c, w, h, st, rank, world, layout);
+  if (rc) return rc;
+  // every frame's CamFrame, before anything is enqueued (the caller's cameras are not read again)
+  CamTable tab;
+  memset(&tab, 0, sizeof tab);
+  for (int f = 0; f < nframes; ++f) {
+    rc = camera_frame(cameras[f], st->camera, w, h, &tab.f[f]);
+    if (rc) {
+      set_error("rt_context_render_cameras_async: camera of frame " + std::to_string(f) + ": " + rt_last_error());
+      return rc;
+    }
+  }
+  auto seed_of = [&](int f) { return seeds ? seeds[f] : st->seed; };
+  auto one_by_one = [&]() {
+    for (int f = 0; f < nframes; ++f) {
+      rt_settings sf = *st;
+      sf.seed = seed_of(f);
+      int r = render_one(c, w, h, &sf, rank, world, layout, d_linear[f], d_rgba ? d_rgba[f] : nullptr, stream, nullptr,
+                         1, &tab.f[f]);
+      if (r) return r;
+    }
+    return (int)RT_OK;
+  };
+  KParams p;
+  base_params(c, w, h, st, rank, world, layout, &p, &tab.f[0]);
+  p.spp_total = st->samples;
+  if (nframes == 1 || use_wavefront(c) || !stream_wanted(c, p, st, nframes)) return one_by_one();
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  rc = enter_stream(c, s);
+  if (rc) return rc;
+  // the set's table in d.cams: written when the set differs from the last one
+  // (the same set again, other seeds, reuses table, generation and schedule)
+  if (c->seq_n != nframes || memcmp(&c->seq_cams, &tab, sizeof tab) != 0) {
+    rc = grow(c, &c->d.cams, sizeof(CamTable));
+    if (rc) return rc;
+    const int e = launch_cam_upload(tab, nframes, c->d.cams.as<CamFrame>(), s);
+    if (e != hipSuccess) {
+      c->seq_n = 0;
+      return launch_failed("camera table", e);
+    }
+    c->seq_cams = tab;
+    c->seq_n = nframes;
+    c->seq_gen = ++c->cam_gen;
+  }
+  // (the shadow-cone rows hold for every frame's rays, or for the launch not at all)
+  for (int f = 1; f < nframes && p.cone_rows_off; ++f)
+    if (!cone_rows_hold(c->flat, tab.f[f].o)) p.cone_rows_off = 0;
+  CamKey key;
+  key.gen = c->seq_gen;
+  key.frames = c->seq_cams.f;
+  key.n = nframes;
+  rc = prepare_schedule(c, &p, st, s, nframes, nullptr, 0, key);
+  if (rc) return rc;
+  p.nframes = nframes;
+  for (int f = 0; f < nframes; ++f) {
+    p.frame_key[f] = rt_rng_seed_key(seed_of(f));
+    p.frame_lin[f] = d_linear[f];
+    p.frame_rgba[f] = d_rgba ? d_rgba[f] : nullptr;
+  }
+  p.num_wgs = p.num_blocks * nframes;
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  bool streamed = false;
+  rc = render_stream(c, p, st, nframes, nframes, s, &streamed, c->d.cams.as<const CamFrame>());
+  if (rc) return rc;
+  // (a rank without tiles, or rows of two frames past the budget: the block
+  // kernel has no camera per frame)
+  if (!streamed) return one_by_one();
+  c->stats.frames += nframes;
+  c->stats.launches += 1;
+  c->stats.batched_launches += 1;
+  return leave_stream(c, s);
+}
+
+// rt_camera_orbit (include/rt_api.h states the formula and its order)
+int rt_camera_orbit(const rt_camera* cam, int32_t n, double degrees, rt_camera* out) {
+  if (!cam || !out || n < 1) {
+    set_error("rt_camera_orbit: cam and out must be given and n >= 1");
+    return RT_E_INVALID;
+  }
+  const double fields[12] = {cam->position[0], cam->position[1], cam->position[2], cam->look_at[0],
+                             cam->look_at[1],  cam->look_at[2],  cam->up[0],       cam->up[1],
+                             cam->up[2],       cam->fov,         cam->aspect_ratio, degrees};
+  for (double v : fields)
+    if (!std::isfinite(v)) {
+      set_error("rt_camera_orbit: the camera's fields and degrees must be finite");
+      return RT_E_INVALID;
+    }
+  const double ul = sqrt(cam->up[0] * cam->up[0] + cam->up[1] * cam->up[1] + cam->up[2] * cam->up[2]);
+  if (!(ul > 0)) {
+    set_error("rt_camera_orbit: up is zero");
+    return RT_E_INVALID;
+  }
+  const double a[3] = {cam->up[0] / ul, cam->up[1] / ul, cam->up[2] / ul};
+  double v[3];
+  for (int k = 0; k < 3; ++k) v[k] = cam->position[k] - cam->look_at[k];
+  const double axv[3] = {a[1] * v[2] - a[2] * v[1], a[2] * v[0] - a[0] * v[2], a[0] * v[1] - a[1] * v[0]};
+  const double adv = a[0] * v[0] + a[1] * v[1] + a[2] * v[2];
+  const rt_camera in = *cam;  // (out may alias cam)
+  for (int32_t k = 0; k < n; ++k) {
+    out[k] = in;
+    if (k == 0) continue;  // bit for bit the input
+    const double th = (degrees * k / n) * (M_PI / 180);
+    const double ct = cos(th), st = sin(th);
+    for (int i = 0; i < 3; ++i)
+      out[k].position[i] = in.look_at[i] + v[i] * ct + axv[i] * st + a[i] * adv * (1 - ct);
+  }
+  return RT_OK;
 }
 
 }  // extern "C"

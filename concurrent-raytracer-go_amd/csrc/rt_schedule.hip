@@ -179,6 +179,62 @@ __global__ __launch_bounds__(64) void sched_pixels(const SchedParams p) {
   }
 }
 
+// K1 of a camera sequence: the same record, a pixel's masks
+// the OR over the sequence's cameras of sched_pixels' masks under camera k
+// (its frame cams[k], within its own tile masks cam_masks[(k * local + lt) * 2
+// ..]).  Each camera's test drops only primitives its rays provably miss, so a
+// pixel with empty masks is missed by every frame's rays: the live-pixel list
+// built from these masks is the union of the frames' lists.  A kernel of its
+// own, so that sched_pixels stays the code it was.
+__global__ __launch_bounds__(64) void sched_pixels_seq(const SchedParams p, const CamFrame* __restrict__ cams, int ncams,
+                                                       const unsigned long long* __restrict__ cam_masks) {
+  const int lt = blockIdx.x >> 4, w = blockIdx.x & 15, lane = threadIdx.x;
+  const int q = w * 64 + lane, t = p.tile_list ? p.tile_list[lt] : p.rank + lt * p.world;
+  unsigned long long ms = 0, mt = 0;
+  if (p.tile_masks) {
+    const int x = (t % p.tiles_x) * 32 + (q & 31), y = (t / p.tiles_x) * 32 + (q >> 5);
+    if (t < p.ntiles && x < p.W && y < p.H) {
+      for (int k = 0; k < ncams; ++k) {
+        const unsigned long long ts = cam_masks[((size_t)k * p.local + lt) * 2];
+        const unsigned long long tt = cam_masks[((size_t)k * p.local + lt) * 2 + 1];
+        if (!(ts | tt)) continue;
+        const CamFrame cf = cams[k];
+        double axis[3], cmin, smax;
+        pixel_cone(cf, p.W, p.H, x, y, axis, &cmin, &smax);
+        for (unsigned long long b = ts & ~ms; b; b &= b - 1) {  // (a bit already set needs no second test)
+          const int i = __builtin_ctzll(b);
+          if (cone_meets_sphere(p.spheres[i].c, p.spheres[i].r, cf.o, axis, cmin, smax)) ms |= 1ull << i;
+        }
+        for (unsigned long long b = tt & ~mt; b; b &= b - 1) {
+          const int i = __builtin_ctzll(b);
+          if (cone_meets_sphere(p.tris[i].bc, p.tris[i].br, cf.o, axis, cmin, smax)) mt |= 1ull << i;
+        }
+      }
+    }
+    p.pixmask[((size_t)lt * 1024 + q) * 2] = ms;
+    p.pixmask[((size_t)lt * 1024 + q) * 2 + 1] = mt;
+  }
+  const unsigned long long live = __ballot((ms | mt) != 0);
+  ms = wave_or(ms);
+  mt = wave_or(mt);
+  if (lane == 0 && p.pilot_blocks) {  // the pilot's block, as sched_pixels writes it
+    int32_t* r = p.pilot_blocks + (size_t)blockIdx.x * kBlockInts;
+    r[0] = lt;
+    r[1] = w * 64;
+    r[2] = 64;
+    r[3] = 0;
+    r[4] = 1;
+    r[5] = -1;
+    r[6] = 1;
+    r[7] = 0;
+    put_u64(r + 8, ms);
+    put_u64(r + 10, mt);
+    put_u64(r + 12, live);
+    r[14] = t;
+    r[15] = 0;
+  }
+}
+
 // K2: per pixel, the estimated path work of one sample.
 template <bool kAdaptive>
 __global__ __launch_bounds__(256) void sched_est(const SchedParams p) {
@@ -565,6 +621,17 @@ int sched_launch_pixels(const SchedParams& p, void* stream) {
   if (e != hipSuccess) return (int)e;
   if (p.active) hipLaunchKernelGGL(sched_pixels<true>, dim3(p.local * 16), dim3(64), 0, s, p);
   else hipLaunchKernelGGL(sched_pixels<false>, dim3(p.local * 16), dim3(64), 0, s, p);
+  return (int)hipGetLastError();
+}
+
+int sched_launch_pixels_seq(const SchedParams& p, const CamFrame* d_cams, int ncams,
+                            const unsigned long long* d_cam_masks, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (p.local <= 0) return hipSuccess;
+  if (p.active || ncams < 1 || !d_cams || (p.tile_masks && !d_cam_masks)) return (int)hipErrorInvalidValue;
+  const hipError_t e = hipMemsetAsync(p.hist, 0, (2 * kBuckets + 4) * sizeof(int32_t), s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(sched_pixels_seq, dim3(p.local * 16), dim3(64), 0, s, p, d_cams, ncams, d_cam_masks);
   return (int)hipGetLastError();
 }
 

@@ -353,13 +353,22 @@ bool cone_masks_apply(const FlatScene& fs) {
   return fs.bvh.empty() && fs.spheres.size() <= 64 && fs.tris.size() <= 64;
 }
 
+double cone_extent(const FlatScene& fs) {
+  double E = vnorm(arr(fs.cam_pos));
+  for (const DSphere& s : fs.spheres) E = fmax(E, vnorm(arr(s.c)) + fabs(s.r));
+  for (const DLight& l : fs.lights) E = fmax(E, vnorm(arr(l.pos)));
+  return E;
+}
+
+bool cone_rows_hold(const FlatScene& fs, const double origin[3]) {
+  return vnorm(arr(origin)) <= 2.0 * cone_extent(fs);  // (a NaN origin: no)
+}
+
 void cone_rows(const FlatScene& fs, std::vector<unsigned long long>* rows) {
   const size_t nl = fs.lights.size(), no = (size_t)fs.objects;
   rows->assign(nl * no, ~0ull);
   if (!cone_masks_apply(fs)) return;
-  double E = vnorm(arr(fs.cam_pos));
-  for (const DSphere& s : fs.spheres) E = fmax(E, vnorm(arr(s.c)) + fabs(s.r));
-  for (const DLight& l : fs.lights) E = fmax(E, vnorm(arr(l.pos)));
+  const double E = cone_extent(fs);
   for (const DSphere& s : fs.spheres)  // (fmax drops a NaN)
     if (!isfinite(s.c[0] + s.c[1] + s.c[2] + s.r)) return;
   for (const DLight& l : fs.lights)

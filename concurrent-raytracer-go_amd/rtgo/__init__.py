@@ -316,6 +316,8 @@ EXPORTED_SYMBOLS = [
     "rt_context_progressive_state",
     "rt_adaptive_step",
     "rt_scene_cone_rows",
+    "rt_context_render_cameras_async",
+    "rt_camera_orbit",
 ]
 
 _lib = None
@@ -431,6 +433,12 @@ def lib():
                                              i32, ctypes.POINTER(Adaptive), ctypes.POINTER(i32)]),
         "rt_camera_frame": (ctypes.c_int, [ctypes.POINTER(Camera), i32, i32, i32, ctypes.POINTER(ctypes.c_double)]),
         "rt_scene_cone_rows": (ctypes.c_int, [ctypes.POINTER(SceneView), i32, ctypes.POINTER(ctypes.c_uint64), sz]),
+        "rt_context_render_cameras_async": (
+            ctypes.c_int,
+            [vp, i32, i32, ctypes.POINTER(Settings), i32, ctypes.POINTER(Camera), ctypes.POINTER(ctypes.c_uint64), i32,
+             i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), vp],
+        ),
+        "rt_camera_orbit": (ctypes.c_int, [ctypes.POINTER(Camera), i32, ctypes.c_double, ctypes.POINTER(Camera)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -805,6 +813,57 @@ class ParallelRenderer:
         }
         return img
 
+    def render_sequence(self, scene: Scene, width: int, height: int, cameras, seeds=None) -> np.ndarray:
+        """The scene from each of ``cameras`` (Camera structs or scene-file camera dicts; any number):
+        an (n, H, W, 4) uint8 array, frame f that of ``render`` with the scene's camera replaced by
+        cameras[f] and seed seeds[f] (None: the renderer's seed), byte for byte.
+        On one device, with a context of its own, in launches of at most RT_MAX_FRAMES frames
+        (Context.render_cameras_async).  ``last_linear`` becomes (n, H, W, 3) float32."""
+        t0 = time.perf_counter()
+        if (len(self.devices) if self.devices else max(1, self.settings.num_devices)) > 1:
+            raise RenderError("render_sequence renders on one device (sequences over several GPUs are not supported)")
+        cams = [_as_camera(c) for c in cameras]
+        n = len(cams)
+        if n < 1:
+            raise RenderError("render_sequence: at least one camera is needed")
+        if seeds is not None and len(seeds) != n:
+            raise RenderError(f"render_sequence: {len(seeds)} seeds for {n} cameras")
+        _check(lib().rt_validate(ctypes.byref(scene.view), width, height, ctypes.byref(self.settings)))
+        import torch
+
+        dev = self.devices[0] if self.devices else 0
+        if self._prog_ctx is None:  # (the context render_progressive uses, kept like the rt_renderer)
+            self._prog_ctx = Context(dev)
+        ctx = self._prog_ctx
+        if self._tuning is not None:
+            ctx.set_tuning(self._tuning)
+        ctx.set_scene(scene)
+        npix = width * height
+        with torch.cuda.device(dev):
+            lin = torch.zeros((n, npix * 3), dtype=torch.float32, device="cuda")
+            rgba = torch.zeros((n, npix * 4), dtype=torch.uint8, device="cuda")
+            for f0 in range(0, n, RT_MAX_FRAMES):
+                f1 = min(n, f0 + RT_MAX_FRAMES)
+                ctx.render_cameras_async(width, height, self.settings, cams[f0:f1],
+                                         [lin[f].data_ptr() for f in range(f0, f1)],
+                                         [rgba[f].data_ptr() for f in range(f0, f1)],
+                                         seeds=None if seeds is None else [int(s) for s in seeds[f0:f1]], stream=0)
+            torch.cuda.synchronize()
+            self.last_linear = lin.cpu().numpy().reshape(n, height, width, 3)
+            img = rgba.cpu().numpy().reshape(n, height, width, 4)
+        self.benchmark_data = {
+            "scene_name": "demo_scene",
+            "resolution": f"{width}x{height}",
+            "render_time_seconds": time.perf_counter() - t0,
+            "samples": self.settings.samples,
+            "max_depth": self.settings.max_depth,
+            "num_workers": self.settings.num_workers,
+            "timestamp": datetime.now(timezone.utc).isoformat(),
+            "features": list(self.FEATURES),
+            "frames": n,
+        }
+        return img
+
     def rank_seconds(self) -> list:
         """Device seconds of each rank's render launches in the last render (load balance)."""
         r = self._renderer()
@@ -876,6 +935,20 @@ class Context:
         rp = (ctypes.c_void_p * n)(*d_rgba) if d_rgba is not None else None
         _check(lib().rt_context_render_frames_async(self._h, width, height, ctypes.byref(settings), n, sd, rank, world,
                                                      layout, lp, rp, ctypes.c_void_p(stream)))
+
+    def render_cameras_async(self, width, height, settings: Settings, cameras, d_linear, d_rgba=None, seeds=None,
+                             stream: int = 0, rank: int = 0, world: int = 1, layout: int = RT_LAYOUT_IMAGE):
+        """rt_context_render_cameras_async: len(cameras) frames of the scene, frame f seen from cameras[f]
+        (Camera structs or scene-file camera dicts) with seed seeds[f] (None: settings.seed), in one
+        streamed launch where a batched launch would stream, else frame by frame (DESIGN.md §4.11);
+        d_linear / d_rgba: per-frame device pointers (d_rgba None: no RGBA8)."""
+        n = len(cameras)
+        cams = (Camera * max(1, n))(*[_as_camera(c) for c in cameras])
+        sd = (ctypes.c_uint64 * n)(*seeds) if seeds is not None else None
+        lp = (ctypes.c_void_p * max(1, n))(*d_linear)
+        rp = (ctypes.c_void_p * max(1, n))(*d_rgba) if d_rgba is not None else None
+        _check(lib().rt_context_render_cameras_async(self._h, width, height, ctypes.byref(settings), n, cams, sd, rank,
+                                                      world, layout, lp, rp, ctypes.c_void_p(stream)))
 
     def progressive_begin(self, width, height, settings: Settings, rank: int = 0, world: int = 1,
                           layout: int = RT_LAYOUT_IMAGE):
@@ -980,20 +1053,42 @@ def tiles_for_rank(width: int, height: int, rank: int, world: int) -> int:
     return lib().rt_tiles_for_rank(width, height, rank, world)
 
 
-def camera_frame(camera, model, width: int, height: int) -> np.ndarray:
-    """rt_camera_frame: the viewport frame of `camera` (a Camera, a Scene, or a scene file's
-    camera dict) under `model` (RT_CAMERA_* or its name) for a width x height image, as 12
-    float64: origin, lower_left, horizontal, vertical."""
+def _as_camera(camera) -> Camera:
+    """A Camera from a Camera, a Scene (its camera) or a scene file's camera dict."""
     if isinstance(camera, Scene):
-        camera = camera.view.camera
-    elif isinstance(camera, dict):
+        return camera.view.camera
+    if isinstance(camera, dict):
         cam = Camera()
         cam.position[:] = camera.get("position", (0, 0, 0))
         cam.look_at[:] = camera.get("lookAt", (0, 0, 0))
         cam.up[:] = camera.get("up", (0, 0, 0))
         cam.fov = camera.get("fov", 0.0)
         cam.aspect_ratio = camera.get("aspectRatio", 0.0)
-        camera = cam
+        return cam
+    return camera
+
+
+def _camera_dict(cam: Camera) -> dict:
+    return {"position": list(cam.position), "lookAt": list(cam.look_at), "up": list(cam.up), "fov": cam.fov,
+            "aspectRatio": cam.aspect_ratio}
+
+
+def camera_orbit(camera, n: int, degrees: float = 360.0) -> list:
+    """rt_camera_orbit: n views on a circle around the camera's lookAt, about its up axis, `degrees`
+    in all (view k is turned by degrees * k / n; view 0 is the camera itself, bit for bit), as a
+    list of scene-file camera dicts.  camera: a Camera, a Scene or a camera dict.  Host only."""
+    n = int(n)
+    cam = _as_camera(camera)
+    out = (Camera * max(1, n))()
+    _check(lib().rt_camera_orbit(ctypes.byref(cam), n, float(degrees), out))
+    return [_camera_dict(out[k]) for k in range(n)]
+
+
+def camera_frame(camera, model, width: int, height: int) -> np.ndarray:
+    """rt_camera_frame: the viewport frame of `camera` (a Camera, a Scene, or a scene file's
+    camera dict) under `model` (RT_CAMERA_* or its name) for a width x height image, as 12
+    float64: origin, lower_left, horizontal, vertical."""
+    camera = _as_camera(camera)
     out = np.zeros(12, np.float64)
     _check(lib().rt_camera_frame(ctypes.byref(camera), CAMERAS.get(model, model), width, height,
                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -458,6 +458,39 @@ int rt_context_render_async(rt_context* ctx, int32_t width, int32_t height, cons
 int rt_context_render_frames_async(rt_context* ctx, int32_t width, int32_t height, const rt_settings* settings,
                                    int32_t nframes, const uint64_t* seeds, int32_t rank, int32_t world,
                                    int32_t layout, float* const* d_linear, uint8_t* const* d_rgba, void* hip_stream);
+
+/* A camera sequence: nframes frames of the context's scene,
+ * frame f seen from cameras[f] -- a turntable, a fly-through, a stereo pair.
+ * Frame f is, byte for byte, what rt_context_render_async writes when the
+ * scene's camera is cameras[f] and settings->seed is seeds[f] (seeds NULL:
+ * settings->seed for every frame); settings->camera picks the camera model for
+ * all frames.  Buffers, layout, rank and world as in
+ * rt_context_render_frames_async.  Where a batched launch of nframes frames
+ * would be streamed (rt_tuning.stream; auto: scenes of spheres alone, two
+ * frames or more) the frames are ONE streamed launch on one work schedule,
+ * whose live pixels are the union over the cameras.  Everything else -- one
+ * frame, BVH scenes on the wavefront path, sample passes, a sky, measuring
+ * schedules, tail helpers, scenes with triangles under the auto rule --
+ * renders FRAME BY FRAME, each frame with its camera in place of the scene's:
+ * correct and slow, with a new work schedule per frame.
+ * RT_E_INVALID, with nothing enqueued and no buffer touched: nframes outside
+ * [1, RT_MAX_FRAMES], NULL cameras or d_linear, and in look-at mode a camera
+ * that rt_camera_frame refuses (the message names the frame's index).  The
+ * cameras are copied before the call returns and no pointer is retained.  The
+ * scene's own camera does not change: later renders show the scene's view.  A
+ * progression of the context is not disturbed. */
+int rt_context_render_cameras_async(rt_context* ctx, int32_t width, int32_t height, const rt_settings* settings,
+                                    int32_t nframes, const rt_camera* cameras, const uint64_t* seeds,
+                                    int32_t rank, int32_t world, int32_t layout,
+                                    float* const* d_linear, uint8_t* const* d_rgba, void* hip_stream);
+/* n views on a circle around the camera's look_at (host only): with a = up
+ * normalised, v = position - look_at and theta_k = (degrees * k / n) * (pi / 180),
+ * out[k] is cam with
+ *   position = look_at + v cos(theta_k) + (a x v) sin(theta_k) + a (a . v) (1 - cos(theta_k))
+ * per component, in plain binary64 in exactly this order; every other field
+ * is copied, and out[0] is cam bit for bit.  RT_E_INVALID for n < 1, a field
+ * or degrees that is not finite, and a zero up. */
+int rt_camera_orbit(const rt_camera* cam, int32_t n, double degrees, rt_camera* out /* n */);
 
 /* Progressive rendering: one frame's samples rendered over
  * several calls, with the image of the samples so far after each.  A context
