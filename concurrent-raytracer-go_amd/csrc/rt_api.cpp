@@ -284,6 +284,29 @@ int rt_scene_cone_rows(const rt_scene* scene, int32_t force_bvh, uint64_t* out, 
   return RT_OK;
 }
 
+int rt_stream_decode(int32_t order, uint32_t frames, uint32_t nlive, uint32_t spp, const uint32_t* entries, size_t n,
+                     uint32_t* out) {
+  if ((order != 0 && order != 1) || frames == 0 || nlive == 0 || spp == 0 || (n > 0 && (!entries || !out))) {
+    set_error("stream decode: order is 0 or 1, frames, nlive and spp are at least 1, entries and out hold n");
+    return RT_E_INVALID;
+  }
+  // (a launch holds fewer than 2^31 entries, so its divisors and entries are below that)
+  bool small = ((frames | nlive | spp) >> 31) == 0;
+  for (size_t j = 0; j < n && small; ++j) small = (entries[j] >> 31) == 0;
+  if (!small) {
+    set_error("stream decode: frames, nlive, spp and every entry are below 2^31");
+    return RT_E_INVALID;
+  }
+  const StreamDecode k = stream_decode_of(order, frames, nlive, spp);  // (as render_stream fills StreamParams::dec)
+  for (size_t j = 0; j < n; ++j) {
+    const StreamEntry en = stream_decode(k, order, entries[j]);
+    out[3 * j] = en.fl;
+    out[3 * j + 1] = en.i;
+    out[3 * j + 2] = en.s;
+  }
+  return RT_OK;
+}
+
 const char* rt_last_error(void) { return g_last_error.c_str(); }
 
 // pinned scene staging made by rt_context_create (grown when a scene needs more)

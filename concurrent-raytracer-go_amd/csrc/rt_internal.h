@@ -362,6 +362,55 @@ struct KParams {
 //   order 1: e = (i * spp + s) * frames + fl  (the frames interleaved)
 // Row of (fl, i, s): (fl * spp + s) * nlive + i, so the resolve's lanes (one
 // per live pixel) read consecutive rows.
+//
+// The decode e -> (fl, i, s) divides twice by launch constants: e by d0, the
+// quotient by d1 (order 0: d0 = spp, d1 = nlive; order 1: d0 = frames,
+// d1 = spp).  The host finds, per divisor d, l = ceil(log2 d) and
+// m = ceil(2^(31 + l) / d) (stream_div_of); m fits 32 bits (d > 2^(l-1) gives
+// m <= 2^32 - 1 for l <= 31, and d = 1 gives 2^31), and
+//   2^(31 + l) <= m d < 2^(31 + l) + d <= 2^(31 + l) + 2^l,
+// which is the condition under which floor(m n / 2^(31 + l)) = floor(n / d)
+// for EVERY n < 2^31 (Granlund & Montgomery 1994, theorem 4.2 with N = 31):
+// the launch's bound on e, and a quotient is no larger.  The kernel forms it
+// as the high word of (2 n) m, shifted right by l: n < 2^31 keeps 2 n in 32
+// bits.  One function for the kernel, the host and the CPU test
+// (rt_stream_decode, include/rt_api.h).
+#if defined(__HIPCC__)
+#define RT_HOST_DEVICE __host__ __device__
+#else
+#define RT_HOST_DEVICE
+#endif
+struct StreamDiv {
+  uint32_t d, m, l, _pad;
+};
+struct StreamDecode {
+  StreamDiv d0, d1;
+};
+struct StreamEntry {
+  uint32_t fl, i, s;  // the launch's frame, the live pixel, the sample
+};
+inline StreamDiv stream_div_of(uint32_t d) {  // 1 <= d < 2^31
+  StreamDiv r{d, 0, 0, 0};
+  while ((1ull << r.l) < d) ++r.l;
+  r.m = (uint32_t)(((1ull << (31 + r.l)) + d - 1) / d);
+  return r;
+}
+inline StreamDecode stream_decode_of(int32_t order, uint32_t frames, uint32_t nlive, uint32_t spp) {
+  // (an empty launch -- no live pixel -- has no entry to decode: any divisor does)
+  const uint32_t a = order == 0 ? spp : frames, b = order == 0 ? nlive : spp;
+  return StreamDecode{stream_div_of(a ? a : 1u), stream_div_of(b ? b : 1u)};
+}
+// (Div, Decode: StreamDiv, StreamDecode in whatever address space the caller holds them)
+template <class Div>
+RT_HOST_DEVICE inline uint32_t stream_div(uint32_t n, const Div& k) {  // n / k.d, n < 2^31
+  return (uint32_t)(((uint64_t)(n << 1) * k.m) >> 32) >> k.l;
+}
+template <class Decode>
+RT_HOST_DEVICE inline StreamEntry stream_decode(const Decode& k, int32_t order, uint32_t e) {
+  const uint32_t t = stream_div(e, k.d0), r0 = e - t * k.d0.d;
+  const uint32_t q = stream_div(t, k.d1), r1 = t - q * k.d1.d;
+  return order == 0 ? StreamEntry{q, r1, r0} : StreamEntry{r0, q, r1};
+}
 struct StreamParams {
   const int32_t* live;         // SchedParams::live (4 ints per live pixel)
   const int32_t* live_pos;     // SchedParams::live_pos
@@ -380,6 +429,9 @@ struct StreamParams {
   // launch shoots from instead of KParams::cf; null: every frame shoots from KParams::cf.  Last, so that
   // no offset of the kernels' argument moves.
   const CamFrame* cams;
+  // the entry decode's divisors and magic numbers (stream_decode_of, per group:
+  // `frames` is the group's); behind cams for the same reason
+  StreamDecode dec;
 };
 struct StreamKArgs {           // the kernels' one argument: KParams at offset 0 (rt_kernel.hip fresh())
   KParams k;

@@ -43,6 +43,7 @@
 //   the hit list, entry -> sample id              HitList::entry_id
 //   phase 2, a pass's refill                      ring_low, resolve_entries, block_entry;
 //                                                 the stream kernel: stream_claim_chunk, stream_entry
+//                                                 (stream_decode, rt_internal.h; stream_cam_stage, stream_cam)
 //   the tail export of pass 0                     tail_reserve, tail_pixel_row, the rest inline (next to
 //                                                 them: tail_helper)
 //   closest hit, lighting, soft shadows, scatter  closest_hit / closest_wide, cone_candidates / cone_wide,
@@ -725,7 +726,10 @@ __device__ __forceinline__ void camera_ray(KArg k, int x, int y, int s, rt_rng& 
 //     wave: 0, 0); r[16 + i] the stamp of shade iteration 4 i (i < 16), or --
 //     when a lone path ran -- its section clocks; r[32..36] / r[37..41]
 //     shade-iteration clocks / counts by live lanes (1, 2, 3-4, 5-8, > 8);
-//     r[42] lone-path bounces, r[43] entries into solo_path;
+//     r[42] lone-path bounces, r[43] entries into solo_path; (a stream wave)
+//     r[44] / r[45] shade iterations whose top-of-loop refill set up at least
+//     one entry / the lanes those served, r[46] / r[47] the same of the
+//     second-pass refill;
 //   a tail helper's record: r[0] start, r[1] first path, r[2] end, r[3] ticks in
 //     solo_path, r[4..6] the last path's start and its depth when exported and
 //     at its end, r[7] paths, r[8] their bounces, r[14] = -1;
@@ -744,6 +748,7 @@ struct WgClock {
   unsigned long long t_start = 0, t_loop = 0, iter = 0;
   unsigned long long sec[5] = {0, 0, 0, 0, 0}, from[5] = {0, 0, 0, 0, 0};  // by WgSection: clocks, start of the open one
   unsigned long long vis = 0, alive = 0, coop = 0, seq = 0;
+  unsigned long long rf_top = 0, rf_top_lanes = 0, rf_second = 0, rf_second_lanes = 0;  // (kStream) refills, see refill()
   // by live lanes (vectors: indexed by a variable, and an array member so
   // indexed would keep the whole struct in scratch)
   typedef unsigned long long Buckets __attribute__((ext_vector_type(5)));
@@ -786,6 +791,18 @@ struct WgClock {
   __device__ __forceinline__ void soft_form(unsigned long long owners) {
     if (__popcll(owners) <= kCoopMax) coop += __popcll(owners); else ++seq;
   }
+  // (kStream) a refill set up the entries of the lanes of `served`: at the top
+  // of a shade iteration, or ahead of its second closest-hit pass
+  __device__ __forceinline__ void refill(bool second, unsigned long long served) {
+    if (served == 0) return;
+    if (second) {
+      rf_second += 1;
+      rf_second_lanes += __popcll(served);
+    } else {
+      rf_top += 1;
+      rf_top_lanes += __popcll(served);
+    }
+  }
   __device__ __forceinline__ void loop_done() {
     t_loop = __builtin_amdgcn_s_memrealtime();
     if (bprev >= 0) bclk[bprev] += __builtin_amdgcn_s_memtime() - bts;
@@ -818,6 +835,10 @@ struct WgClock {
         for (int i = 0; i < 16; ++i) r[16 + i] = solo_clk[i];
       r[42] = block ? solo_clk[6] : 0;  // lone-path bounces (0: none ran)
       r[43] = block ? solo_clk[7] : 0;  // entries into solo_path
+      r[44] = rf_top;
+      r[45] = rf_top_lanes;
+      r[46] = rf_second;
+      r[47] = rf_second_lanes;
     }
   }
   __device__ __forceinline__ void stream_write(int lane) const { write(fresh(), lane, false, 0, 0); }
@@ -865,6 +886,7 @@ struct WgClock {
   __device__ __forceinline__ void end(WgSection) {}
   __device__ __forceinline__ void hit_done() {}
   __device__ __forceinline__ void soft_form(unsigned long long) {}
+  __device__ __forceinline__ void refill(bool, unsigned long long) {}
   __device__ __forceinline__ void loop_done() {}
   __device__ __forceinline__ void write(KArg, int, bool, unsigned long long, unsigned long long) const {}
   __device__ __forceinline__ void stream_write(int) const {}
@@ -1835,22 +1857,62 @@ __device__ __forceinline__ uint2 stream_claim_chunk() {
 // own CamFrame, row frame0 + fl of the launch's table in device memory (one
 // load per lane: with order 1 neighbouring lanes hold different frames); only
 // here, at entry set-up -- nothing after the camera ray reads a camera.
+// The decode of e is stream_decode (rt_internal.h): two multiply-highs by the
+// magic numbers render_stream put into StreamParams::dec, exact for every
+// e < 2^31.  The launch's CamK comes from LDS (stream_cam_lds below) unless
+// every frame has a camera of its own.
+//
+// (not kCams) The launch-uniform CamK, all but its key: make_cam's values,
+// computed once per wave ahead of the loop (stream_cam_stage, before the
+// barrier that ends the staging) and read back per entry set-up -- the same
+// operations in the same order on the same inputs, so the same bits, without
+// the two refined reciprocals, the conversions and the corner per refill and
+// without a VGPR across the loop.  A function's array, as tput_lds.
+constexpr int kCamLds = 7;  // dW, dH, rW, rH, llcx, llcy, llcz
+__device__ __forceinline__ double* stream_cam_lds() {
+  __shared__ double camk[kCamLds];
+  return camk;
+}
+__device__ __forceinline__ void stream_cam_stage() {
+  const SArg sk = sfresh();
+  const CamK ck = make_cam(0, sk->k.W, sk->k.H, sk->k.cf);
+  if (threadIdx.x == 0) {
+    double* c = stream_cam_lds();
+    c[0] = ck.dW;
+    c[1] = ck.dH;
+    c[2] = ck.rW;
+    c[3] = ck.rH;
+    c[4] = ck.llcx;
+    c[5] = ck.llcy;
+    c[6] = ck.llcz;
+  }
+}
+__device__ __forceinline__ CamK stream_cam(uint64_t fkey) {
+  const SArg sk = sfresh();
+  const double* c = stream_cam_lds();
+  CamK r;
+  r.key = fkey;
+  r.W = (uint32_t)sk->k.W;
+  r.lookat = sk->k.cf.model;
+  r.dW = c[0];
+  r.dH = c[1];
+  r.rW = c[2];
+  r.rH = c[3];
+  r.llcx = c[4];
+  r.llcy = c[5];
+  r.llcz = c[6];
+  r.vw = sk->k.cf.h[0];
+  r.ox = sk->k.cf.o[0];
+  r.oy = sk->k.cf.o[1];
+  r.oz = sk->k.cf.o[2];
+  return r;
+}
 template <bool kBase, bool kCams>
 __device__ __forceinline__ int stream_entry(unsigned e, rt_rng& rng, d3& o, d3& d, uint64_t (&skey)[64]) {
   const SArg sk = sfresh();
   const unsigned spp = (unsigned)sk->k.spp, nlive = (unsigned)sk->s.nlive;
-  unsigned fl, i, s;
-  if (sk->s.order == 0) {
-    const unsigned t = e / spp;
-    s = e - t * spp;
-    fl = t / nlive;
-    i = t - fl * nlive;
-  } else {
-    const unsigned nf = (unsigned)sk->s.frames, t = e / nf;
-    fl = e - t * nf;
-    i = t / spp;
-    s = t - i * spp;
-  }
+  const StreamEntry en = stream_decode(sk->s.dec, sk->s.order, e);
+  const unsigned fl = en.fl, i = en.i, s = en.s;
   const int4 it = reinterpret_cast<const int4*>(sk->s.live)[i];
   const uint64_t fkey = sk->k.frame_key[sk->s.frame0 + (int)fl];
   Counters nc;
@@ -1859,8 +1921,7 @@ __device__ __forceinline__ int stream_entry(unsigned e, rt_rng& rng, d3& o, d3& 
     const CamFrame& cf = sk->s.cams[sk->s.frame0 + (int)fl];
     camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, cf), cf, it.x, it.y, (int)fs, rng, o, d, nc);
   } else {
-    camera_ray_c<false>(make_cam(fkey, sk->k.W, sk->k.H, sk->k.cf), sk->k.cf,
-                        it.x, it.y, (int)fs, rng, o, d, nc);
+    camera_ray_c<false>(stream_cam(fkey), sk->k.cf, it.x, it.y, (int)fs, rng, o, d, nc);
   }
   skey[lane_now()] = rt_soft_key(fkey, (uint32_t)it.y * (uint32_t)sk->k.W + (uint32_t)it.x, (uint32_t)fs);
   return (int)((fl * spp + s) * nlive + i);
@@ -2034,6 +2095,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
     uint4* dst = reinterpret_cast<uint4*>(dyn_lds);
     for (int i = lane; i < pk.stage_bytes / 16; i += 64) dst[i] = src[i];
   }
+  if constexpr (kStream && !kCams) stream_cam_stage();  // (stream_entry reads it: behind the barrier)
   __syncthreads();
 
   Counters c, culled;
@@ -2214,6 +2276,37 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
       r_[2] = slot[q_][2];                                            \
     }                                                                 \
   } while (0)
+    // HitRecord of the closest primitive `hs` of the lane's ray (sphere.go:42-58,
+    // triangle.go:68-81).  The block kernels fill it where the pass finds the
+    // hit.  kStream: only `hs` is kept across the passes, and the record of
+    // both passes' hits is filled once behind them -- a lane that hit keeps
+    // its o and d until the scatter, so the expressions see the same values;
+    // one run at the width of both passes' hitters instead of two at half of
+    // it each, and P, N, front, mi and self are not live through the second
+    // pass.  (A macro, as the accessors above.)
+#define hit_record(gg_)                                                 \
+  do {                                                                  \
+    if (!hit_is_tri(hs)) {                                              \
+      const DSphere& S0 = (gg_).spheres[hs.idx];                        \
+      const double t = hs.num / len2(d);                                \
+      P = o + muls(d, t);                                               \
+      d3 outward = divs(P - ld3(S0.c), S0.r);                           \
+      front = dot(d, outward) < 0;                                      \
+      N = front ? outward : neg(outward);                               \
+      mi = S0.mat;                                                      \
+      self = S0.obj;                                                    \
+    } else if constexpr (!kSph) {                                       \
+      const DTri& T0 = (gg_).tris[hs.idx];                              \
+      P = o + muls(d, hs.num);                                          \
+      double w = 1.0 - hs.u - hs.v;                                     \
+      d3 n = ld3(T0.n);                                                 \
+      N = normalize((muls(n, w) + muls(n, hs.u)) + muls(n, hs.v));      \
+      front = dot(d, N) < 0;                                            \
+      if (!front) N = neg(N);                                           \
+      mi = T0.mat;                                                      \
+      self = T0.obj;                                                    \
+    }                                                                   \
+  } while (0)
     for (;;) {
       // (1) closest hit (hitWorld, renderer.go:170), in up to two passes: a
       // lane whose ray missed (or reached the depth cut-off) finishes at once
@@ -2237,6 +2330,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           // when the claimed chunk runs out it claims the next one in the
           // same pass (two rounds at most).  No wave ever waits for another.
           unsigned long long fm = __ballot(!alive);
+          const unsigned long long fm0 = fm;
           for (int r = 0; r < 2 && fm != 0; ++r) {
             if (qbeg == qend) {
               if (dry) break;
@@ -2266,6 +2360,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
             qbeg = min(qend, qbeg + (unsigned)__popcll(fm));
             fm = __ballot(!alive);
           }
+          clk.refill(pass > 0, fm0 & ~fm);
         }
         const unsigned long long freem = kStream ? 0ull : __ballot(!alive);
         int limit = kStream ? 0 : min(nh, resolved + kRound);
@@ -2425,7 +2520,14 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           // than the short scan they split; measured on the 5-sphere scene)
           if (h.g.nt == 0 && h.g.ns >= 16 && nq > 0 && nq <= 16) {
             // (kCount: helpers count their sphere tests, primary queries included)
-            wide_found = closest_wide<kCount, kSph>(h.g, need, qm, nq, o, d, hs, wide_fb, c);
+            if constexpr (kStream) {
+              // (closest_wide writes every lane's hit: the first pass's hitters keep theirs for the record)
+              HitK hw;
+              wide_found = closest_wide<kCount, kSph>(h.g, need, qm, nq, o, d, hw, wide_fb, c);
+              if (need) hs = hw;
+            } else {
+              wide_found = closest_wide<kCount, kSph>(h.g, need, qm, nq, o, d, hs, wide_fb, c);
+            }
             wide_q = true;
           }
         }
@@ -2456,27 +2558,8 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
           } else {
             shade = true;
             cnt<kCount>(c, C_SHADE);
-            // HitRecord of the closest primitive (sphere.go:42-58, triangle.go:68-81)
-            if (!hit_is_tri(hs)) {
-              const DSphere& S0 = gg.spheres[hs.idx];
-              const double t = hs.num / len2(d);
-              P = o + muls(d, t);
-              d3 outward = divs(P - ld3(S0.c), S0.r);
-              front = dot(d, outward) < 0;
-              N = front ? outward : neg(outward);
-              mi = S0.mat;
-              self = S0.obj;
-            } else if constexpr (!kSph) {
-              const DTri& T0 = gg.tris[hs.idx];
-              P = o + muls(d, hs.num);
-              double w = 1.0 - hs.u - hs.v;
-              d3 n = ld3(T0.n);
-              N = normalize((muls(n, w) + muls(n, hs.u)) + muls(n, hs.v));
-              front = dot(d, N) < 0;
-              if (!front) N = neg(N);
-              mi = T0.mat;
-              self = T0.obj;
-            }
+            // (kStream: one hit record per iteration, behind the passes)
+            if constexpr (!kStream) hit_record(gg);
           }
         }
         // a second pass when enough lanes are free and entries are left
@@ -2487,6 +2570,9 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
       if (outer == 1) continue;
       if (outer == 2) break;
 
+      if constexpr (kStream) {
+        if (shade) hit_record((hot<kStage, kSph>().g));
+      }
       clk.hit_done();
       if (__ballot(shade) != 0) {
         // (2) calculateDirectLighting (renderer.go:229-297), light by light
@@ -2674,6 +2760,7 @@ __device__ __forceinline__ void render_body(const KParams& pk) {
 #undef set_path_T
 #undef path_q
 #undef stream_store_row
+#undef hit_record
   clk.loop_done();
   if constexpr (kStream) {
     // every row of this wave's paths is written; resolve_rows_kernel, the next

@@ -460,6 +460,7 @@ static int render_stream(rt_context* c, const KParams& p, const rt_settings* st,
     sp.frame0 = f0;
     sp.frames = std::min(group, nframes - f0);
     sp.total = (uint32_t)((size_t)sp.frames * per_entries);
+    sp.dec = stream_decode_of(sp.order, (uint32_t)sp.frames, (uint32_t)sp.nlive, (uint32_t)p.spp);
     const int e = launch_stream(p, sp, wave_slots, s);
     if (e != hipSuccess) return launch_failed("stream", e);
     c->stats.stream_launches += 1;

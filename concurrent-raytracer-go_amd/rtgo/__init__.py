@@ -318,6 +318,7 @@ EXPORTED_SYMBOLS = [
     "rt_scene_cone_rows",
     "rt_context_render_cameras_async",
     "rt_camera_orbit",
+    "rt_stream_decode",
 ]
 
 _lib = None
@@ -439,6 +440,8 @@ def lib():
              i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), vp],
         ),
         "rt_camera_orbit": (ctypes.c_int, [ctypes.POINTER(Camera), i32, ctypes.c_double, ctypes.POINTER(Camera)]),
+        "rt_stream_decode": (ctypes.c_int, [i32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.POINTER(ctypes.c_uint32), sz, ctypes.POINTER(ctypes.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1103,6 +1106,16 @@ def cone_rows(scene: Scene, force_bvh: int = 0) -> np.ndarray:
     _check(lib().rt_scene_cone_rows(ctypes.byref(scene.view), force_bvh,
                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), out.size))
     return out[: nl * no].reshape(nl, no)
+
+
+def stream_decode(order: int, frames: int, nlive: int, spp: int, entries) -> np.ndarray:
+    """rt_stream_decode: (n, 3) uint32 -- the (frame, live pixel, sample) of each queue entry of a
+    streamed launch, decoded by the stream kernel's own function (host only)."""
+    e = np.ascontiguousarray(entries, np.uint32)
+    out = np.zeros((max(e.size, 1), 3), np.uint32)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    _check(lib().rt_stream_decode(order, frames, nlive, spp, e.ctypes.data_as(u32p), e.size, out.ctypes.data_as(u32p)))
+    return out[: e.size]
 
 
 def render(scene: Scene, width: int, height: int, settings: Settings):

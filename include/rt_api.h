@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -298,6 +298,17 @@ int rt_camera_frame(const rt_camera* cam, int32_t model, int32_t width, int32_t 
  * has no shadow-cone masks (a tree, more than 64 spheres, more than 64
  * triangles). */
 int rt_scene_cone_rows(const rt_scene* scene, int32_t force_bvh, uint64_t* out, size_t capacity);
+
+/* The stream kernel's entry decode (host only, no device): entry entries[j] of
+ * a streamed launch of `frames` frames, `nlive` live pixels and `spp` samples
+ * in entry order `order` (rt_tuning.stream_order: 0 e = (frame * nlive + pixel)
+ * * spp + sample, 1 e = (pixel * spp + sample) * frames + frame) as the kernel
+ * decodes it -- the same function, with the multiply-high magic numbers the
+ * launch computes -- into out[3 j .. 3 j + 2] = frame, live pixel, sample.
+ * frames, nlive, spp in [1, 2^31) and every entry below 2^31 (a launch's own
+ * bound), or RT_E_INVALID. */
+int rt_stream_decode(int32_t order, uint32_t frames, uint32_t nlive, uint32_t spp, const uint32_t* entries, size_t n,
+                     uint32_t* out);
 
 /* ------------------------------------------ persistent multi-GPU renderer */
 

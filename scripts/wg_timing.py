@@ -110,6 +110,16 @@ print(f"  lighting split: cone+hard {hard.sum() / tot:.1%}  soft {soft.sum() / t
       f"{(light.sum() - hard.sum() - soft.sum()) / tot:.1%};  scatter {scat.sum() / tot:.1%}")
 print(f"  lanes alive per shade iteration {alive.sum() / max(it.sum(), 1):.1f}; coop owners {coop.sum():.0f}, "
       f"soft_seq passes {seq.sum():.0f}")
+# a stream wave's refills (words 44..47): shade iterations whose refill set up
+# at least one entry, and the lanes those served -- at the top of the iteration
+# and ahead of its second closest-hit pass
+rft, rftl, rfs, rfsl = (d[:, :, k].astype(np.float64).sum() for k in (44, 45, 46, 47))
+if rft + rfs > 0:
+    n_it = max(it.sum(), 1)
+    print(f"  stream refills: top of the iteration in {rft:.0f} iterations ({rft / n_it:.1%}), {rftl:.0f} lanes "
+          f"({rftl / max(rft, 1):.1f} per refill, {rftl / n_it:.2f} per iteration); second pass in {rfs:.0f} "
+          f"iterations ({rfs / n_it:.1%}), {rfsl:.0f} lanes ({rfsl / max(rfs, 1):.1f} per refill, "
+          f"{rfsl / n_it:.2f} per iteration)")
 for i in order[:6]:
     for w in range(WPG):
         npx, ns = int(d[i, w, 13]) >> 16, int(d[i, w, 13]) & 0xFFFF
