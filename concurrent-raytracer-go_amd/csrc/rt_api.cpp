@@ -307,6 +307,20 @@ int rt_stream_decode(int32_t order, uint32_t frames, uint32_t nlive, uint32_t sp
   return RT_OK;
 }
 
+static_assert(kSoftUndecided == RT_SOFT_UNDECIDED && kSoftMiss == RT_SOFT_MISS && kSoftHit == RT_SOFT_HIT, "rt_api.h");
+int rt_soft_screen(const double* centers, const double* r2, const double* origins, const double* dirs, const double* il,
+                   const double* tmin, const double* tmax, size_t n, int32_t* out) {
+  if (n > 0 && (!centers || !r2 || !origins || !dirs || !il || !tmin || !tmax || !out)) {
+    set_error("soft screen: every array holds n cases");
+    return RT_E_INVALID;
+  }
+  for (size_t j = 0; j < n; ++j) {
+    const double *c = centers + 3 * j, *o = origins + 3 * j, *u = dirs + 3 * j;
+    out[j] = soft_screen(c[0], c[1], c[2], r2[j], o[0], o[1], o[2], u[0], u[1], u[2], il[j], tmin[j], tmax[j]);
+  }
+  return RT_OK;
+}
+
 const char* rt_last_error(void) { return g_last_error.c_str(); }
 
 // pinned scene staging made by rt_context_create (grown when a scene needs more)

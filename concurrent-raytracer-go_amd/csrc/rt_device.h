@@ -216,6 +216,21 @@ __device__ __forceinline__ bool root_out(double num, double a, double inv_a, dou
   return q < tmin || tmax < q;
 }
 
+// RT_WG_TIMING builds count the soft shadows' trace passes (rt_kernel.hip
+// soft_pass_done): soft_note marks a pass -- with the soft-ray screen
+// (RT_SOFT_SCREEN) where a lane runs the exact test, without it where a lane
+// gets past Sphere.Hit's `discriminant < 0`.  Nothing in any other build.
+#ifndef RT_SOFT_SCREEN
+#define RT_SOFT_SCREEN 1
+#endif
+#ifdef RT_WG_TIMING
+__shared__ unsigned int soft_note_flag;
+__shared__ unsigned long long soft_pass_cnt[2];  // trace passes; those of them that were marked
+__device__ __forceinline__ void soft_note() { soft_note_flag = 1; }
+#else
+__device__ __forceinline__ void soft_note() {}
+#endif
+
 // Sphere.Hit (sphere.go:22-40) as a range query: which root Go accepts.
 // Returns 0 = miss, 1 = first root, 2 = second root.
 __device__ __forceinline__ int sphere_query(const DSphere& S, d3 o, d3 d, double a, double inv_a, double tmin,
@@ -225,6 +240,7 @@ __device__ __forceinline__ int sphere_query(const DSphere& S, d3 o, d3 d, double
   double c = (ocx * ocx + ocy * ocy + ocz * ocz) - S.r2;
   double disc = hb * hb - a * c;
   if (disc < 0) return 0;
+  if (!RT_SOFT_SCREEN) soft_note();
   double sq = sqrt(disc);
   double n1 = -hb - sq;
   if (!root_out(n1, a, inv_a, tmin, tmax)) {

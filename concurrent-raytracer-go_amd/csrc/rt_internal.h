@@ -411,6 +411,63 @@ RT_HOST_DEVICE inline StreamEntry stream_decode(const Decode& k, int32_t order, 
   const uint32_t q = stream_div(t, k.d1), r1 = t - q * k.d1.d;
   return order == 0 ? StreamEntry{q, r1, r0} : StreamEntry{r0, q, r1};
 }
+// A screen in front of the exact test of a SOFT shadow ray (DESIGN.md §4.7,
+// "Soft rays decided without normalising them").  Only the occlusion boolean
+// of such a ray is used, and in real arithmetic Sphere.Hit's boolean does not
+// depend on the direction's length: with u the unnormalised direction, il an
+// approximation of 1 / |u|, oc = P - c, h = (oc.u) il, cc = |oc|^2 - r^2, the
+// ray P + t u/|u| meets the sphere where g(t) = t^2 + 2 h t + cc = 0, and
+// g(t) = (t + h)^2 - D with D = h^2 - cc.  Each test below is "surely ...":
+// it carries a margin over the magnitudes of its terms -- eps on those that
+// il's error moves (|il |u| - 1| <= kSoftScreenIl), eps2 on |oc|^2 + r^2,
+// which only rounding moves -- at least 16 times what il and the screen's own
+// roundings can add up to and thousands of times the reference's roundings
+// (the proof is in DESIGN.md), so a sure answer is the boolean Sphere.Hit
+// (sphere.go:22-40) returns on the reference's normalised ray; anything else
+// -- a grazing ray, a root near tmin or tmax, NaN, infinity (every comparison
+// with one is false) -- is undecided and the caller runs the exact test.  The
+// operations are explicit fused multiply-adds: the same bits on the host and
+// in the kernel (rt_soft_screen, include/rt_api.h, runs this function).
+constexpr int kSoftScreenBits = 17;      // eps = 2^-17 >= 16 (2 kSoftScreenIl + 12 * 2^-53): the terms il's error moves (h^2: twice)
+constexpr int kSoftScreenBits2 = 16;     // eps2 = eps 2^-16 = 2^-33 >= 2^16 * 14 * 2^-53: the terms only rounding moves
+constexpr double kSoftScreenIl = 2e-7;   // il from v_rsq_f32 of the binary32-rounded |u|^2 (1 ulp), |u|^2 in [0.81, 1.21]
+enum SoftScreen { kSoftUndecided = 0, kSoftMiss = 1, kSoftHit = 2 };
+// x / eps, exact (a test reads `x / eps > magnitudes`: the shift is an inline
+// operand of v_ldexp_f64, where eps as a factor would hold a register pair)
+RT_HOST_DEVICE inline double soft_scaled(double x) { return __builtin_ldexp(x, kSoftScreenBits); }
+RT_HOST_DEVICE inline int soft_screen(double cx, double cy, double cz, double r2, double px, double py, double pz,
+                                      double ux, double uy, double uz, double il, double tmin, double tmax) {
+  // the guards.  Of the interval (the same for every candidate of a ray): not
+  // empty, tmin far above the underflow range; of the magnitudes: with
+  // tmax < 2^500 and |oc|^2 + r^2 < 2^1000 nothing overflows, here or in the
+  // reference.  A NaN fails them or every comparison below.
+  if (!(tmin >= 0x1p-40 && tmin <= tmax && tmax < 0x1p500)) return kSoftUndecided;
+  const double ocx = px - cx, ocy = py - cy, ocz = pz - cz;
+  const double o2 = __builtin_fma(ocz, ocz, __builtin_fma(ocy, ocy, ocx * ocx));
+  const double h = __builtin_fma(ocz, uz, __builtin_fma(ocy, uy, ocx * ux)) * il;
+  const double cc = o2 - r2, q = o2 + __builtin_fabs(r2);
+  if (!(q < 0x1p1000)) return kSoftUndecided;
+  // (cc cancels when P is on the sphere, so the margins carry q -- at eps2: il does not touch cc)
+  const double q2 = __builtin_ldexp(q, -kSoftScreenBits2);
+  const double D = soft_scaled(__builtin_fma(h, h, -cc)), mD = __builtin_fma(h, h, q2);
+  if (-D > mD) return kSoftMiss;  // no real root, and the reference's discriminant is negative too
+  const double ah = __builtin_fabs(h);
+  const double g0 = soft_scaled(__builtin_fma(tmin, __builtin_fma(2.0, h, tmin), cc));
+  const double m0 = __builtin_fma(tmin, __builtin_fma(2.0, ah, tmin), q2);
+  const double g1 = soft_scaled(__builtin_fma(tmax, __builtin_fma(2.0, h, tmax), cc));
+  const double m1 = __builtin_fma(tmax, __builtin_fma(2.0, ah, tmax), q2);
+  const bool p0 = g0 > m0, n0 = -g0 > m0, p1 = g1 > m1, n1 = -g1 > m1;
+  if ((p0 && n1) || (n0 && p1)) return kSoftHit;  // exactly one root inside: Hit takes the first root in range, else the second
+  if (n0 && n1) return kSoftMiss;                 // the interval lies between the roots
+  if (p0 && p1) {
+    // t + h: t's side of the vertex -h
+    const double v0 = soft_scaled(tmin + h), v1 = soft_scaled(tmax + h), w0 = tmin + ah, w1 = tmax + ah;
+    if (v0 > w0 || -v1 > w1) return kSoftMiss;            // both roots, if any, on one side of the interval
+    if (-v0 > w0 && v1 > w1 && D > mD) return kSoftHit;   // both roots inside
+  }
+  return kSoftUndecided;
+}
+
 struct StreamParams {
   const int32_t* live;         // SchedParams::live (4 ints per live pixel)
   const int32_t* live_pos;     // SchedParams::live_pos

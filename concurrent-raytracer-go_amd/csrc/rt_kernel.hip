@@ -238,6 +238,51 @@ __device__ __forceinline__ bool shadow_blocked(const Geo& p, bool masks, d3 o, d
   return any_hit<kCount, kSph, kMix>(p, o, d, tmax, stack, c);
 }
 
+// Occlusion of one SOFT shadow ray, from P towards ldir + 0.1 pt, in the
+// spheres-only stream kernels: only the boolean leaves this
+// code, so the candidates first go through soft_screen (rt_internal.h) on the
+// unnormalised direction u and a binary32 1 / |u|.  |u|^2 lies in [0.81, 1.21]
+// (ldir a unit vector, |pt| < 1); v_rsq_f32 is good to 1 ulp (AMD Instinct
+// CDNA ISA guide) and its argument is |u|^2 rounded to binary32, so
+// |il |u| - 1| < 2^-23 + 2^-25 + 2^-51 < kSoftScreenIl.  The first sure hit
+// makes the ray occluded, sure misses of every candidate make it
+// unoccluded; only a lane with an undecided candidate and no sure hit
+// normalises the ray and runs the exact test as before, behind a branch the
+// wave skips when it has no such lane.
+template <bool kCount, bool kMix>
+__device__ __forceinline__ bool soft_blocked_sph(const Geo& p, bool masks, d3 P, d3 ldir, d3 pt, double ldist, CandS m,
+                                                 int* stack, Counters& c) {
+  if (RT_SOFT_SCREEN && masks) {
+    const d3 u = ldir + muls(pt, 0.1);
+    const double il = (double)__builtin_amdgcn_rsqf((float)__builtin_fma(u.z, u.z, __builtin_fma(u.y, u.y, u.x * u.x)));
+    bool undecided = false;
+    for (unsigned long long b = m.s; b; b &= b - 1) {
+      const DSphere& S = p.spheres[__builtin_ctzll(b)];
+      const int r = soft_screen(S.c[0], S.c[1], S.c[2], S.r2, P.x, P.y, P.z, u.x, u.y, u.z, il, 0.001, ldist);
+      if (r == kSoftHit) return true;
+      undecided |= r == kSoftUndecided;
+    }
+    if (!undecided) return false;
+    soft_note();
+  }
+  return shadow_blocked<kCount, true, kMix>(p, masks, P, normalize(ldir + muls(pt, 0.1)), ldist, m, stack, c);
+}
+// (RT_WG_TIMING builds) a trace pass of soft_queue or soft_coop starts, ends
+__device__ __forceinline__ void soft_pass_begin(int lane) {
+#ifdef RT_WG_TIMING
+  if (lane == 0) soft_note_flag = 0;
+#endif
+}
+__device__ __forceinline__ void soft_pass_done(int lane) {
+#ifdef RT_WG_TIMING
+  if (lane == 0) {
+    soft_pass_cnt[0] += 1;
+    soft_pass_cnt[1] += soft_note_flag;
+    soft_note_flag = 0;
+  }
+#endif
+}
+
 // ------------------------------------------------------------ wide mode
 // When few lanes of a wave still run paths (the end of a block, where one
 // long path sets the launch's critical path), the idle lanes help: every
@@ -394,7 +439,9 @@ __device__ __forceinline__ CandS cand_of_lane(CandS m, int ow) { return CandS{rl
 template <bool kCount, bool kSph = false, bool kMix = false>
 __device__ __forceinline__ CoopOut soft_coop(const Geo p, bool masks, bool trace, d3 P, d3 ldir, double ldist,
                              typename Kind<kSph>::C cm, uint64_t x, const uint64_t* jump, int* stack, Counters& c) {
-  const int lane = (int)(threadIdx.x & 63);
+  // (kSph: read where it is used -- the jump table's byte offset of the lane
+  // is otherwise kept in a register pair through the whole bounce loop)
+  const int lane = kSph ? lane_now() & 63 : (int)(threadIdx.x & 63);
   int need = 16, unocc = 0, tries = 0;
   while (need > 0) {
     const uint64_t x0 = state_at3(x, jump, lane), x1 = x0 * RT_PCG_MULT + RT_PCG_INC,
@@ -409,9 +456,15 @@ __device__ __forceinline__ CoopOut soft_coop(const Geo p, bool masks, bool trace
     // tries consumed: up to and including the last chosen one
     const int used = nch == need ? 64 - __clzll(chm) : 64;
     bool occ = false;
-    if (chosen && trace)
-      occ = shadow_blocked<kCount, kSph, kMix>(p, masks, P, normalize(ldir + muls(unit_ball_point(o0, o1, o2), 0.1)), ldist,
-                                         cm, stack, c);
+    if constexpr (kSph) {
+      if (trace) soft_pass_begin(lane);
+      if (chosen && trace) occ = soft_blocked_sph<kCount, kMix>(p, masks, P, ldir, unit_ball_point(o0, o1, o2), ldist, cm, stack, c);
+      if (trace) soft_pass_done(lane);
+    } else {
+      if (chosen && trace)
+        occ = shadow_blocked<kCount, kSph, kMix>(p, masks, P, normalize(ldir + muls(unit_ball_point(o0, o1, o2), 0.1)), ldist,
+                                           cm, stack, c);
+    }
     unocc += nch - __popcll(__ballot(chosen && occ));
     need -= nch;
     tries += used;
@@ -543,11 +596,17 @@ __device__ __forceinline__ int soft_queue(const Geo& p, bool masks, bool need_so
       typename Kind<kSph>::C co;
       co.s = __shfl(cm.s, ow);
       if constexpr (!kSph) co.t = p.nt ? __shfl(cm.t, ow) : 0ull;  // (no triangles: cm.t is 0)
+      if constexpr (kSph) soft_pass_begin(lane);
       if (lane < n) {
         const d3 pt = mk(rt_bits_to_unit(e.x) * 2 - 1, rt_bits_to_unit(e.y) * 2 - 1, rt_bits_to_unit(e.z) * 2 - 1);
-        if (!shadow_blocked<kCount, kSph, kMix>(p, masks, Po, normalize(Lo + muls(pt, 0.1)), dist, co, stack, c))
-          atomicAdd(&sq_unocc[ow], 1);
+        bool blocked;
+        if constexpr (kSph)
+          blocked = soft_blocked_sph<kCount, kMix>(p, masks, Po, Lo, pt, dist, co, stack, c);
+        else
+          blocked = shadow_blocked<kCount, kSph, kMix>(p, masks, Po, normalize(Lo + muls(pt, 0.1)), dist, co, stack, c);
+        if (!blocked) atomicAdd(&sq_unocc[ow], 1);
       }
+      if constexpr (kSph) soft_pass_done(lane);
       head += n;
       __syncthreads();
     }
@@ -723,7 +782,9 @@ __device__ __forceinline__ void camera_ray(KArg k, int x, int y, int s, rt_rng& 
 //     counts: hit, lighting, soft, phase 1 (visibility), shade iterations,
 //     cone + hard shadow, scatter, lane-iterations alive, coop owners served,
 //     soft_queue passes; r[13] np * 65536 + ns, r[14] split slot + 1 (a stream
-//     wave: 0, 0); r[16 + i] the stamp of shade iteration 4 i (i < 16), or --
+//     wave: 0, 0); r[15] the soft shadows' trace passes (soft_pass_done), and
+//     shifted left by 32 those of them that a lane marked (soft_note,
+//     rt_device.h); r[16 + i] the stamp of shade iteration 4 i (i < 16), or --
 //     when a lone path ran -- its section clocks; r[32..36] / r[37..41]
 //     shade-iteration clocks / counts by live lanes (1, 2, 3-4, 5-8, > 8);
 //     r[42] lone-path bounces, r[43] entries into solo_path; (a stream wave)
@@ -762,6 +823,7 @@ struct WgClock {
   __device__ __forceinline__ unsigned long long* record(KArg k) const { return k->dbg + (size_t)blockIdx.x * kDbgStride; }
   __device__ __forceinline__ void start(int lane) {
     if (lane < 16) solo_clk[lane] = 0;
+    if (lane < 2) soft_pass_cnt[lane] = 0;
     t_start = __builtin_amdgcn_s_memrealtime();
     vis = __builtin_amdgcn_s_memtime();
   }
@@ -827,6 +889,7 @@ struct WgClock {
       r[12] = seq;
       r[13] = shape;
       r[14] = split;
+      r[15] = soft_pass_cnt[0] | soft_pass_cnt[1] << 32;
       for (int i = 0; i < 5; ++i) {
         r[32 + i] = bclk[i];
         r[37 + i] = bcnt[i];

@@ -319,6 +319,7 @@ EXPORTED_SYMBOLS = [
     "rt_context_render_cameras_async",
     "rt_camera_orbit",
     "rt_stream_decode",
+    "rt_soft_screen",
 ]
 
 _lib = None
@@ -442,6 +443,7 @@ def lib():
         "rt_camera_orbit": (ctypes.c_int, [ctypes.POINTER(Camera), i32, ctypes.c_double, ctypes.POINTER(Camera)]),
         "rt_stream_decode": (ctypes.c_int, [i32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                              ctypes.POINTER(ctypes.c_uint32), sz, ctypes.POINTER(ctypes.c_uint32)]),
+        "rt_soft_screen": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 7 + [sz, ctypes.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1116,6 +1118,25 @@ def stream_decode(order: int, frames: int, nlive: int, spp: int, entries) -> np.
     u32p = ctypes.POINTER(ctypes.c_uint32)
     _check(lib().rt_stream_decode(order, frames, nlive, spp, e.ctypes.data_as(u32p), e.size, out.ctypes.data_as(u32p)))
     return out[: e.size]
+
+
+SOFT_UNDECIDED, SOFT_MISS, SOFT_HIT = 0, 1, 2
+
+
+def soft_screen(centers, r2, origins, dirs, il, tmin, tmax) -> np.ndarray:
+    """rt_soft_screen: (n,) int32 -- per case SOFT_MISS / SOFT_HIT where the stream kernels' screen of a soft
+    shadow ray is sure, SOFT_UNDECIDED where the exact test decides (host only; the kernels' own function).
+    centers, origins, dirs (unnormalised): (n, 3); r2, il (the caller's 1 / |dir|), tmin, tmax: (n,) or scalars."""
+    c, o, u = (np.ascontiguousarray(a, np.float64).reshape(-1, 3) for a in (centers, origins, dirs))
+    n = c.shape[0]
+    assert o.shape[0] == n and u.shape[0] == n, (c.shape, o.shape, u.shape)
+    s = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), (n,))) for a in (r2, il, tmin, tmax)]
+    out = np.zeros(max(n, 1), np.int32)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _check(lib().rt_soft_screen(c.ctypes.data_as(dp), s[0].ctypes.data_as(dp), o.ctypes.data_as(dp), u.ctypes.data_as(dp),
+                                s[1].ctypes.data_as(dp), s[2].ctypes.data_as(dp), s[3].ctypes.data_as(dp), n,
+                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return out[:n]
 
 
 def render(scene: Scene, width: int, height: int, settings: Settings):

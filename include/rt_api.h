@@ -310,6 +310,21 @@ int rt_scene_cone_rows(const rt_scene* scene, int32_t force_bvh, uint64_t* out, 
 int rt_stream_decode(int32_t order, uint32_t frames, uint32_t nlive, uint32_t spp, const uint32_t* entries, size_t n,
                      uint32_t* out);
 
+/* The screen the spheres-only stream kernels put in front of the exact test of
+ * a soft shadow ray (host only, no device; the same function the kernels
+ * run).  Case j: the sphere of centre centers[3 j ..] and squared radius
+ * r2[j], the ray from origins[3 j ..] along the UNNORMALISED direction
+ * dirs[3 j ..], il[j] the caller's approximation of 1 / |dir|, over
+ * [tmin[j], tmax[j]].  out[j] is RT_SOFT_MISS or RT_SOFT_HIT when the screen
+ * is sure -- then Sphere.Hit on the normalised ray returns that boolean,
+ * provided |il |dir| - 1| <= 2e-7 -- and RT_SOFT_UNDECIDED otherwise (always
+ * for a NaN or an infinity in any input). */
+#define RT_SOFT_UNDECIDED 0
+#define RT_SOFT_MISS 1
+#define RT_SOFT_HIT 2
+int rt_soft_screen(const double* centers, const double* r2, const double* origins, const double* dirs, const double* il,
+                   const double* tmin, const double* tmax, size_t n, int32_t* out);
+
 /* ------------------------------------------ persistent multi-GPU renderer */
 
 /* The ParallelRenderer object itself (NewParallelRenderer, renderer.go:54-65,

@@ -120,6 +120,15 @@ if rft + rfs > 0:
           f"({rftl / max(rft, 1):.1f} per refill, {rftl / n_it:.2f} per iteration); second pass in {rfs:.0f} "
           f"iterations ({rfs / n_it:.1%}), {rfsl:.0f} lanes ({rfsl / max(rfs, 1):.1f} per refill, "
           f"{rfsl / n_it:.2f} per iteration)")
+# the soft shadows' trace passes (word 15: the count, and shifted left by 32
+# the passes a lane marked -- with the soft-ray screen a lane that ran the exact
+# test, in a build without it (-DRT_SOFT_SCREEN=0) a lane that got past
+# Sphere.Hit's `discriminant < 0`)
+sp = d[:, :, 15].astype(np.int64)
+sp_all, sp_marked = float((sp & 0xFFFFFFFF).sum()), float((sp >> 32).sum())
+if sp_all > 0:
+    print(f"  soft trace passes {sp_all:.0f} ({sp_all / max(it.sum(), 1):.2f} per shade iteration); marked "
+          f"{sp_marked:.0f} ({sp_marked / sp_all:.1%})")
 for i in order[:6]:
     for w in range(WPG):
         npx, ns = int(d[i, w, 13]) >> 16, int(d[i, w, 13]) & 0xFFFF
