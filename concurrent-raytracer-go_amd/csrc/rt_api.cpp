@@ -230,16 +230,22 @@ int rt_debug_xlane_faults(int32_t device, int32_t reset, uint64_t* out) {
   }
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipDeviceSynchronize());
-  const long long a = xlane_faults_kernel(reset != 0), b = xlane_faults_wavefront(reset != 0);
-  if (a == -1 || b == -1) {
-    set_error("not a cross-lane checking build (make xlane)");
-    return RT_E_INVALID;
+  // every unit that includes rt_device.h and shuffles
+  const long long n[3] = {xlane_faults_kernel(reset != 0), xlane_faults_stream(reset != 0),
+                          xlane_faults_wavefront(reset != 0)};
+  uint64_t sum = 0;
+  for (const long long v : n) {
+    if (v == -1) {
+      set_error("not a cross-lane checking build (make xlane)");
+      return RT_E_INVALID;
+    }
+    if (v < 0) {
+      set_error("reading the cross-lane fault counters failed");
+      return RT_E_DEVICE;
+    }
+    sum += (uint64_t)v;
   }
-  if (a < 0 || b < 0) {
-    set_error("reading the cross-lane fault counters failed");
-    return RT_E_DEVICE;
-  }
-  *out = (uint64_t)(a + b);
+  *out = sum;
   return RT_OK;
 }
 
@@ -351,6 +357,8 @@ int rt_context_create(int32_t device, rt_context** out) {
     if ((int)loaded.size() < n) loaded.resize(n, false);
     if (!loaded[device]) {
       hipError_t e = (hipError_t)preload_render_kernels();
+      if (e == hipSuccess) e = (hipError_t)preload_stream_kernels();
+      if (e == hipSuccess) e = (hipError_t)preload_image_kernels();
       if (e == hipSuccess) e = (hipError_t)preload_sched_kernels();
       if (e == hipSuccess) e = (hipError_t)preload_wf_kernels();
       if (e != hipSuccess) {

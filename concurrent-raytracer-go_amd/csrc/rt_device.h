@@ -1,5 +1,6 @@
 // rt_device.h — device code shared by the gfx950 kernels of the renderer
-// core: the megakernel (rt_kernel.hip) and the wavefront path for BVH scenes
+// core: the megakernel (rt_body.h and the headers it includes; its kernels in
+// rt_kernel.hip and rt_stream.hip) and the wavefront path for BVH scenes
 // (rt_wavefront.hip).  Vec3 arithmetic (internal/math/vector.go), Go's math
 // semantics, the intersection tests (Sphere.Hit, Triangle.Hit), BVH
 // traversal, and Material.Scatter — all binary64 in the reference's order
@@ -33,6 +34,25 @@ __device__ __forceinline__ T rt_checked_shfl(T v, int src, int width = 64) {
 }
 #define __shfl(...) rt_checked_shfl(__VA_ARGS__)
 #endif
+namespace rtgo {
+// The count of the translation unit that calls it (static: each unit reads its
+// own variable), zeroed when `reset`; -1 in a normal build, -2 when a copy
+// failed.  A unit's xlane_faults_* (rt_internal.h) is this one call.
+static inline long long xlane_faults_unit(bool reset) {
+#ifdef RT_CHECK_XLANE
+  unsigned long long v = 0;
+  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_xlane_faults), sizeof v) != hipSuccess) return -2;
+  if (reset) {
+    const unsigned long long z = 0;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_xlane_faults), &z, sizeof z) != hipSuccess) return -2;
+  }
+  return (long long)v;
+#else
+  (void)reset;
+  return -1;
+#endif
+}
+}  // namespace rtgo
 
 namespace rtgo {
 
@@ -216,7 +236,7 @@ __device__ __forceinline__ bool root_out(double num, double a, double inv_a, dou
   return q < tmin || tmax < q;
 }
 
-// RT_WG_TIMING builds count the soft shadows' trace passes (rt_kernel.hip
+// RT_WG_TIMING builds count the soft shadows' trace passes (rt_shadow.h
 // soft_pass_done): soft_note marks a pass -- with the soft-ray screen
 // (RT_SOFT_SCREEN) where a lane runs the exact test, without it where a lane
 // gets past Sphere.Hit's `discriminant < 0`.  Nothing in any other build.

@@ -1,6 +1,8 @@
 // rt_internal.h — host-side interfaces between the C ABI (rt_api.cpp and the
-// files around rt_context.h), the kernels (rt_kernel.hip), the scene loader (scene_json.cpp), the BVH
-// builder (bvh.cpp) and the output writers (image_io.cpp).
+// files around rt_context.h), the kernels (rt_kernel.hip, rt_stream.hip,
+// rt_image_ops.hip, rt_wavefront.hip, rt_schedule.hip, rt_adaptive.hip), the
+// scene loader (scene_json.cpp), the BVH builder (bvh.cpp) and the output
+// writers (image_io.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -490,7 +492,7 @@ struct StreamParams {
   // `frames` is the group's); behind cams for the same reason
   StreamDecode dec;
 };
-struct StreamKArgs {           // the kernels' one argument: KParams at offset 0 (rt_kernel.hip fresh())
+struct StreamKArgs {           // the kernels' one argument: KParams at offset 0 (rt_blocks.h fresh())
   KParams k;
   StreamParams s;
 };
@@ -513,6 +515,8 @@ int stream_wave_slots(int device, int kernel, size_t shmem);
 // Enqueue the render kernel; returns hipError_t as int.
 int launch_render(const KParams& p, bool count, void* stream);
 size_t render_shmem(const KParams& p);
+// a launch of one frame: frame entry 0 from the single-frame fields (launch_render, launch_stream)
+void single_frame_entry(KParams& p);
 // device -> mapped pinned host memory by a kernel (16-byte aligned, a multiple of 16 bytes)
 int launch_download(const void* d_src, void* h_dst_mapped, size_t bytes, void* stream);
 // one workgroup that sleeps for `ms` of device time, then exits (the
@@ -677,10 +681,13 @@ int preload_render_kernels();
 // An empty launch and a 4-KB copy each way on the stream (dev4k: 4 KB of
 // device memory): the runtime's first-launch and first-copy set-up.
 int warm_device(void* stream, void* dev_buf, void* host_pinned, void* host_pageable, size_t bytes);
+int preload_stream_kernels();
+int preload_image_kernels();
 int preload_sched_kernels();
 int preload_wf_kernels();
 // RT_CHECK_XLANE builds: inactive-lane __shfl reads per file (-1: not such a build)
 long long xlane_faults_kernel(bool reset);
+long long xlane_faults_stream(bool reset);
 long long xlane_faults_wavefront(bool reset);
 int wf_lds_nodes(int stack_depth, int nodes, int block, int wgs_per_cu);
 int wf_launch_resolve(const WfParams& p, int npix, void* stream);

@@ -380,7 +380,7 @@ int prepare_schedule(rt_context* c, KParams* p, const rt_settings* st, hipStream
   // counters per frame a launch renders (`frames`), laid out as [copies of
   // the rows][copies of the bits][copies of the counters].  Bits and counters
   // start at zero; each launch's last sub-block of a pixel zeroes them again
-  // (rt_kernel.hip), so they are cleared only when the layout changes.
+  // (rt_body.h), so they are cleared only when the layout changes.
   const size_t rows = (size_t)c->nsplit * st->samples * 3 * sizeof(double);
   const size_t flags = split_flags_bytes(c->nsplit, st->samples);
   if (c->nsplit && c->split_frames < frames) {

@@ -2,7 +2,7 @@
 //
 // Produced on the host by flatten_scene() (scene_flat.cpp) from the boundary's
 // rt_scene (objects-level, like scene.Scene, internal/scene/scene.go:12-16)
-// and read by the gfx950 kernels (rt_kernel.hip).  Everything the reference
+// and read by the gfx950 kernels (rt_body.h, rt_wavefront.hip).  Everything the reference
 // recomputes per test but which depends only on the scene is precomputed
 // here with the reference's own expressions, so the values are bit-identical:
 //   - triangle edges v1-v0, v2-v0 (triangle.go:37-38) and the face normal

@@ -52,7 +52,7 @@ __device__ __forceinline__ int bucket_of(double est) {
 
 // Does the cone (apex, unit axis, cos/sin of its half-angle) meet the sphere
 // (c, r)?  Conservative: radius inflated by ~1e-7, far above binary64
-// rounding of the ray directions (same test as the shadow cones, rt_kernel.hip).
+// rounding of the ray directions (same test as the shadow cones, rt_shadow.h).
 __device__ bool cone_meets_sphere(const double* c, double r, const double* apex, const double* axis, double cos_t,
                                   double sin_t) {
   const double v0 = c[0] - apex[0], v1 = c[1] - apex[1], v2 = c[2] - apex[2];

@@ -1,7 +1,7 @@
 // rt_wavefront.hip — the wavefront path for BVH scenes (> 64 spheres, configs
 // C4/C5: 10k spheres).  DESIGN.md §4.2.
 //
-// The megakernel (rt_kernel.hip) keeps a whole path in one lane: its binary64
+// The megakernel (rt_body.h) keeps a whole path in one lane: its binary64
 // path state costs 168 VGPRs, so a SIMD holds 3 waves, and on a 10k-sphere
 // scene its lanes spend most of the time masked off while the longest
 // traversal of the wave finishes.  Here traceRay's bounce loop
@@ -922,7 +922,7 @@ __global__ RT_TRAV_ATTR void wf_occlude4(const WfParams p) {
 
 // ---------------------------------------------------------------- cones
 // Soft shadows through shadow cones (the BVH form of the megakernel's cone
-// culling, rt_kernel.hip in_cone).  calculateSmartShadow's 16 soft rays of a
+// culling, rt_shadow.h in_cone).  calculateSmartShadow's 16 soft rays of a
 // (path, light) all leave the hit point P inside the cone of half-angle
 // asin(0.1) around lightDir and end at the light (renderer.go:311-320).  A
 // sphere that cannot meet that cone segment cannot block any of them, so the
@@ -1131,7 +1131,7 @@ __global__ __launch_bounds__(kWfBlock) void wf_conegen(const WfParams p) {
 // LDS tree of the occlusion kernels): every sphere of every leaf the cone's
 // node tests reach gets cone_keeps; candidates go to the cone's list, up to
 // kWfConeK (one more ends the walk: the cone's rays are traced instead).
-// The hit sphere itself is left out as in cone_candidates (rt_kernel.hip)
+// The hit sphere itself is left out as in cone_candidates (rt_shadow.h)
 // when the cone leaves its front face at a clear angle.
 // kMix: the lists stay lists of spheres.  A cone that reaches a cube whose
 // bounding sphere (DBox.bc, br) passes the same test ends as "too many
@@ -1661,7 +1661,7 @@ __device__ __forceinline__ void shade_body(const WfParams& p) {
       const DMat* __restrict__ m = p.mats + S0.mat;
       if constexpr (kMix) {
         if (tri) {
-          // triangle.go:68-81 with the megakernel's expressions (rt_kernel.hip
+          // triangle.go:68-81 with the megakernel's expressions (rt_body.h
           // render_body); u, v from wf_extend (kTriHit).  (The sphere record
           // above was formed from sphere 0 of the scene buffer and is dropped.)
           const DTri& T0 = p.g.tris[p.hidx[slot] & ~kTriHit];
@@ -2095,19 +2095,6 @@ int wf_launch_resolve(const WfParams& p, int npix, void* stream) {
 
 // Cross-lane reads from inactive lanes counted by this file's kernels in an
 // RT_CHECK_XLANE build (rt_device.h); -1 in a normal build.  reset: zero it.
-long long xlane_faults_wavefront(bool reset) {
-#ifdef RT_CHECK_XLANE
-  unsigned long long v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_xlane_faults), sizeof v) != hipSuccess) return -2;
-  if (reset) {
-    const unsigned long long z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_xlane_faults), &z, sizeof z) != hipSuccess) return -2;
-  }
-  return (long long)v;
-#else
-  (void)reset;
-  return -1;
-#endif
-}
+long long xlane_faults_wavefront(bool reset) { return xlane_faults_unit(reset); }
 
 }  // namespace rtgo

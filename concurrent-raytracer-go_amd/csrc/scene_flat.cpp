@@ -142,7 +142,7 @@ static void push_tri(FlatScene* fs, v3 v0, v3 v1, v3 v2, int mat, int obj) {
   put(t.e1, e1);
   put(t.e2, e2);
   put(t.n, normalize(cross(e1, e2)));  // NewTriangle, triangle.go:13-34
-  // bounding sphere for the shadow-cone culling (rt_kernel.hip); any
+  // bounding sphere for the shadow-cone culling (rt_shadow.h); any
   // rounding here is covered by the kernel's inflation margins
   const v3 bc = divs(add(add(v0, v1), v2), 3.0);
   double br = 0;
@@ -269,7 +269,7 @@ void flatten_scene(const rt_scene& s, FlatScene* fs) {
 }
 
 // ---------------------------------------------------------------- shadow-cone rows
-// Which spheres can ever be a shadow-cone candidate (rt_kernel.hip in_cone)
+// Which spheres can ever be a shadow-cone candidate (rt_shadow.h in_cone)
 // of a hit on sphere A under light L?  The hit point P lies on A, so every
 // shadow ray of (A, L) stays in one solid that depends on the scene alone,
 // and a sphere clear of it is never admitted.

@@ -1,7 +1,7 @@
 /*
  * rt_adaptive.h — the stop rule of an adaptive progression,
  * one inline function shared by the device kernel that applies it
- * (adaptive_update_kernel, rt_kernel.hip) and the host entry point that
+ * (adaptive_update_kernel, rt_adaptive.hip) and the host entry point that
  * restates it for one pixel (rt_adaptive_step, include/rt_api.h).
  *
  * Integers only: the rule reads a pixel's displayed RGBA8 before and after an

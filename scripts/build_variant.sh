@@ -32,12 +32,15 @@ if [ $# -gt 0 ]; then
   done
   SRC="$SCR/concurrent-raytracer-go_amd/csrc"
 fi
-for k in rt_kernel rt_wavefront rt_schedule; do
+KERNELS="rt_kernel rt_stream rt_wavefront rt_schedule"
+OBJS=""
+for k in $KERNELS; do
   /opt/rocm/bin/hipcc $HIPFLAGS $DEFS -I"$SRC" -x hip -c $SRC/$k.hip -o "$OUT/$k.o" &
+  OBJS="$OBJS $OUT/$k.o"
 done
 wait
-OBJS="$OUT/rt_kernel.o $OUT/rt_wavefront.o $OUT/rt_schedule.o"
-for o in rt_adaptive rt_api rt_render rt_wavefront_host rt_progressive rt_partition scene_json image_io bvh schedule rt_multi \
+# (rt_image_ops: no ray code, no knob: the main build's object)
+for o in rt_image_ops rt_adaptive rt_api rt_render rt_wavefront_host rt_progressive rt_partition scene_json image_io bvh schedule rt_multi \
          scene_flat dev_pool; do OBJS="$OBJS build/$o.o"; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/librtgo.so" $OBJS -L/opt/rocm/lib -lrccl -lz \
   -Wl,-soname,librtgo.so -Wl,-rpath,/opt/rocm/lib

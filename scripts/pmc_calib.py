@@ -3,7 +3,7 @@
 
 MI355X_MICROARCH.md calibrates WRITE_SIZE only for 16-B-per-lane stores; the
 render kernel's epilogue writes a pixel as one 12-B float3 store plus one
-4-B RGBA8 store per lane.  unpack_kernel (rt_kernel.hip) writes exactly that
+4-B RGBA8 store per lane.  unpack_kernel (rt_image_ops.hip) writes exactly that
 pattern, one thread per image pixel, fully coalesced: W*H*16 bytes per
 launch, and reads the same 16 B per pixel from the packed share.  Run under
 rocprofv3 --pmc WRITE_SIZE (and FETCH_SIZE) by scripts/profile.sh; the

@@ -140,7 +140,7 @@ for i in order[:6]:
 for i in order[:4]:
     # slots 16..31: s_memrealtime at every 4th shade iteration, unless the
     # workgroup ran a lone path (slot 42 != 0): then the kernel stores the lone
-    # path's section clocks there instead (rt_kernel.hip, RT_WG_TIMING epilogue)
+    # path's section clocks there instead (rt_wg_clock.h, WgClock::write)
     if d[i, 0, 42] != 0:
         print(f"    WG {int(i)} ran a lone path ({int(d[i, 0, 42])} bounces): its section clocks",
               [int(v) for v in d[i, 0, 16:32]])

@@ -99,7 +99,7 @@ def spheres10k_scene(rtgo, n=10000):
 
 
 def _edge_scenes():
-    """Scenes at the edges of the kernel's exact culling (rt_kernel.hip
+    """Scenes at the edges of the kernel's exact culling (rt_shadow.h
     in_cone / cone_candidates, rt_schedule.hip pixel cones): their margins
     are relative (1e-7 .. 1e-5), so these stress huge radii, far
     coordinates, tiny spheres and a light almost on a surface."""
@@ -173,7 +173,7 @@ def _cube_scenes():
     scenes put hit points on the inner faces of glass / dielectric cubes, the
     camera inside a cube, lights inside and outside cubes, and cubes with
     negative sizes (mirrored: their normals point out), so every shadow-ray
-    shortcut of the kernels (rt_kernel.hip cone_candidates: the hit object's
+    shortcut of the kernels (rt_shadow.h cone_candidates: the hit object's
     self-exclusion; box slab pruning; quiet lights; primary-ray masks) meets
     both orientations."""
     def sph(p, r, m):

@@ -1,7 +1,7 @@
 """CPU: the shadow-cone rows (rt_scene_cone_rows, scene_flat.cpp cone_rows).
 
 A row of (light, hit sphere) has to be a SUPERSET of what the kernels' cone
-test (rt_kernel.hip in_cone) can admit for any hit point on that sphere under
+test (rt_shadow.h in_cone) can admit for any hit point on that sphere under
 that light: the spheres-only stream kernels test only the spheres of the row,
 and their candidate mask stays what it was only while that holds.  Here
 in_cone is restated in binary64 with its two binary32 roots taken 2e-7 wide

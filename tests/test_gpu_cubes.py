@@ -4,7 +4,7 @@ createCube (internal/scene/scene.go:150-190) winds its triangles so that
 calculateNormal (internal/geometry/triangle.go:29-33) points INTO the box, so
 FrontFace (triangle.go:70-73) is true for a hit from inside.  The kernels'
 shadow-cone culling leaves the hit object out of its own shadow rays only
-when the hit is on the object's OUTSIDE (rt_kernel.hip box_self_out): a ray
+when the hit is on the object's OUTSIDE (rt_shadow.h box_self_out): a ray
 that leaves an inner face toward an outside light must still cross the box
 (calculateSmartShadow, renderer.go:299-331).  These scenes reach that case
 through glass and dielectric cubes, a camera inside a cube, lights inside

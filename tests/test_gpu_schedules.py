@@ -65,7 +65,7 @@ def test_measured_recut_does_not_change_the_image(tun):
 def test_split_pixels_across_frames_of_one_renderer():
     """Split pixels keep per-launch hit bits and sub-block counters that the
     last sub-block of each pixel zeroes again for the next launch (no memset
-    per frame, rt_kernel.hip).  Three frames of one renderer with the same
+    per frame, rt_body.h).  Three frames of one renderer with the same
     schedule (seeds 4, 5, 4; nearly every pixel split) all equal the oracle."""
     scene = load_case(rtgo, ("json", None))
     w, h = 40, 24
