@@ -6,7 +6,7 @@
 //             [--sky default|white|sunset|night] [--camera reference|lookat]
 //             [--pass-samples N [--time-budget SECONDS] [--converge PIXELS]
 //              [--adaptive TOL[,PATIENCE[,MIN]]] [--count-map FILE]]
-//             [--orbit N[,DEGREES]]
+//             [--orbit N[,DEGREES]] [--aov PREFIX]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -31,7 +31,22 @@
 // (rt_camera_orbit; --camera lookat makes the views differ in direction too),
 // as camera sequences of at most RT_MAX_FRAMES frames, and writes
 // <stem>_0000<ext> .. ; benchmark_data.json records "frames": N.
+// --aov PREFIX (one view, --samples >= 1) writes, after the
+// render, the first-hit feature buffers of the frame (the render's size,
+// samples, seed and camera model; device 0) as PREFIX.albedo, PREFIX.normal,
+// PREFIX.depth, PREFIX.coverage and PREFIX.object with the output image's
+// extension (PNG, or P3 PPM for ".ppm"), 8 bits per channel, round(v) =
+// floor(v + 0.5):
+//   albedo    round(clamp01(a) * 255) per channel
+//   normal    round(clamp01(n * 0.5 + 0.5) * 255) per channel
+//   depth     grey round(255 * (far - d) / (far - near)), near and far the least and the largest finite
+//             depth of the frame (nearer is brighter); a miss 0; every finite depth equal: 255
+//   coverage  grey round(c * 255)
+//   object    the bytes 0..2 of (index + 1) * 2654435761 mod 2^32, each with its top bit set; a miss black
+// A size without pixels (a width or height <= 0) writes none.  Without --aov
+// nothing changes.
 #include <errno.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -42,6 +57,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -335,8 +351,91 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
   return RT_OK;
 }
 
+// --aov PREFIX: the first-hit feature buffers of the frame (DESIGN.md §4.12,
+// rt_context_render_aov_async) on device 0, with the render's size, samples,
+// seed and camera model, written as five images PREFIX.<name><ext> with the
+// mappings of the usage text above.
+static uint8_t aov_byte(double v) {  // round(clamp01(v) * 255), halves up; NaN: 0
+  if (!(v > 0)) return 0;
+  if (v > 1) v = 1;
+  return (uint8_t)floor(v * 255.0 + 0.5);
+}
+static int write_aov(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, const std::string& prefix,
+                     const std::string& ext) {
+  const size_t npix = (size_t)w * (size_t)h;
+  rt_context* ctx = nullptr;
+  int rc = rt_context_create(0, &ctx);
+  if (rc != RT_OK) return rc;
+  rc = rt_context_set_scene(ctx, scene, 0);
+  // one device block: albedo | normal | depth | coverage | object
+  float* d = nullptr;
+  std::vector<float> host(npix * 9);
+  if (rc == RT_OK && hipMalloc((void**)&d, npix * 9 * sizeof(float)) != hipSuccess) {
+    fprintf(stderr, "hipMalloc failed\n");
+    rc = RT_E_DEVICE;
+  }
+  if (rc == RT_OK) {
+    const rt_aov_buffers out = {d, d + npix * 3, d + npix * 6, d + npix * 7, (int32_t*)(d + npix * 8)};
+    rc = rt_context_render_aov_async(ctx, w, h, &st, nullptr, &out, nullptr);
+  }
+  if (rc == RT_OK && hipMemcpy(host.data(), d, npix * 9 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    fprintf(stderr, "hipMemcpy failed\n");
+    rc = RT_E_DEVICE;
+  }
+  const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
+  if (d) (void)hipFree(d);
+  rt_context_destroy(ctx);
+  if (rc != RT_OK) {
+    if (!err.empty()) fprintf(stderr, "%s\n", err.c_str());
+    return rc;
+  }
+  const float *albedo = host.data(), *normal = albedo + npix * 3, *depth = albedo + npix * 6,
+              *coverage = albedo + npix * 7;
+  const int32_t* object = reinterpret_cast<const int32_t*>(albedo + npix * 8);
+  double near = INFINITY, far = -INFINITY;  // over the frame's finite depths
+  for (size_t i = 0; i < npix; ++i)
+    if (std::isfinite(depth[i])) {
+      near = std::min(near, (double)depth[i]);
+      far = std::max(far, (double)depth[i]);
+    }
+  std::vector<uint8_t> img(npix * 4);
+  const char* names[5] = {"albedo", "normal", "depth", "coverage", "object"};
+  for (int k = 0; k < 5; ++k) {
+    for (size_t i = 0; i < npix; ++i) {
+      uint8_t* px = &img[4 * i];
+      px[3] = 255;
+      if (k == 0) {
+        for (int c = 0; c < 3; ++c) px[c] = aov_byte(albedo[3 * i + c]);
+      } else if (k == 1) {
+        for (int c = 0; c < 3; ++c) px[c] = aov_byte((double)normal[3 * i + c] * 0.5 + 0.5);
+      } else if (k == 2) {
+        uint8_t g = 0;  // a miss
+        if (std::isfinite(depth[i])) g = far > near ? aov_byte((far - (double)depth[i]) / (far - near)) : 255;
+        px[0] = px[1] = px[2] = g;
+      } else if (k == 3) {
+        px[0] = px[1] = px[2] = aov_byte(coverage[i]);
+      } else {
+        // a fixed colour per hittable index: the bytes of (index + 1) * 2654435761 mod 2^32,
+        // each with its top bit set (never black); a miss is black
+        const uint32_t hsh = ((uint32_t)object[i] + 1u) * 2654435761u;
+        for (int c = 0; c < 3; ++c) px[c] = object[i] < 0 ? 0 : (uint8_t)(((hsh >> (8 * c)) & 0xFFu) | 0x80u);
+      }
+    }
+    const std::string fp = prefix + "." + names[k] + ext;
+    printf("Saving to: %s\n", fp.c_str());
+    fflush(stdout);
+    rc = ext == ".ppm" ? rt_write_ppm(fp.c_str(), img.data(), w, h) : rt_write_png(fp.c_str(), img.data(), w, h);
+    if (rc != RT_OK) {
+      printf("Error saving image: %s\n", rt_last_error());
+      return rc;
+    }
+  }
+  return RT_OK;
+}
+
 int main(int argc, char** argv) {
   std::vector<std::string> args;
+  std::string aov_prefix;      // --aov PREFIX (empty: no feature buffers)
   long long orbit_n = 0;       // --orbit N[,DEGREES] (0: one render)
   double orbit_deg = 360.0;
   double watchdog_s = 0;  // --watchdog (0: no bound, as Go's Render)
@@ -445,6 +544,12 @@ int main(int argc, char** argv) {
       orbit_n = v;
     } else if (a == "--count-map") {  // --adaptive: the per-pixel sample counts as a grey PNG
       count_map = need("--count-map");
+    } else if (a == "--aov") {  // the first-hit feature buffers as five images PREFIX.<name><ext>
+      aov_prefix = need("--aov");
+      if (aov_prefix.empty()) {
+        fprintf(stderr, "invalid --aov (a file name prefix)\n");
+        return 2;
+      }
     } else if (a == "--sky") {  // opt-in sky on miss (atmosphere.go presets); default: black
       const std::string k = need("--sky");
       if (k == "none") st.sky = RT_SKY_NONE;
@@ -470,6 +575,10 @@ int main(int argc, char** argv) {
   }
   if (orbit_n > 0 && (pass_samples > 0 || adaptive_on || st.num_devices > 1)) {
     fprintf(stderr, "--orbit renders whole frames on one device: not with --pass-samples, --adaptive or --devices > 1\n");
+    return 2;
+  }
+  if (!aov_prefix.empty() && (orbit_n > 0 || st.samples < 1)) {
+    fprintf(stderr, "--aov needs --samples >= 1 and one view (not with --orbit)\n");
     return 2;
   }
   if (pass_samples > 0 && st.num_devices > 1) {
@@ -631,6 +740,11 @@ int main(int argc, char** argv) {
       rt_scene_free(sb);
       return 1;
     }
+    if (!aov_prefix.empty() &&
+        write_aov(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, aov_prefix, ext_of(out_path)) != RT_OK) {
+      rt_scene_free(sb);
+      return 1;
+    }
     rt_settings done_st = st;
     done_st.samples = rendered;  // (the samples actually rendered)
     save_benchmark(out_path, w, h, done_st, stats, adaptive_on ? mean_samples : -1);
@@ -678,6 +792,11 @@ int main(int argc, char** argv) {
                                   : rt_write_png(out_path.c_str(), rgba.data(), (int32_t)w, (int32_t)h);
   if (rc != RT_OK) {
     printf("Error saving image: %s\n", rt_last_error());
+    rt_renderer_destroy(rr);
+    rt_scene_free(sb);
+    return 1;
+  }
+  if (!aov_prefix.empty() && write_aov(scene, (int32_t)w, (int32_t)h, st, aov_prefix, ext_of(out_path)) != RT_OK) {
     rt_renderer_destroy(rr);
     rt_scene_free(sb);
     return 1;

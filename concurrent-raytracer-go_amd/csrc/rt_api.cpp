@@ -94,6 +94,8 @@ static int validate_settings(const rt_settings* st, int32_t w, int32_t h) {
   return RT_OK;
 }
 
+int check_settings(const rt_settings* st, int32_t w, int32_t h) { return validate_settings(st, w, h); }
+
 int check_frame(const rt_context* c, int32_t w, int32_t h, const rt_settings* st) {
   const int rc = validate_settings(st, w, h);
   if (rc) return rc;
@@ -361,6 +363,7 @@ int rt_context_create(int32_t device, rt_context** out) {
       if (e == hipSuccess) e = (hipError_t)preload_image_kernels();
       if (e == hipSuccess) e = (hipError_t)preload_sched_kernels();
       if (e == hipSuccess) e = (hipError_t)preload_wf_kernels();
+      if (e == hipSuccess) e = (hipError_t)preload_aov_kernels();
       if (e != hipSuccess) {
         set_error(std::string("kernel code object load failed: ") + hipGetErrorString(e));
         return RT_E_DEVICE;

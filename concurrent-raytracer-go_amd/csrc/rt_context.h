@@ -312,6 +312,8 @@ inline bool use_wavefront(const rt_context* c) { return !c->flat.bvh.empty() && 
 // st, the image size and the scene's camera under st's camera model (a
 // degenerate look-at camera is RT_E_INVALID): what every planner and render
 // entry point checks; check_frame_args: the scene, those, rank/world, layout.
+// (check_settings: st and the size alone, for a call that brings its own camera)
+int check_settings(const rt_settings* st, int32_t w, int32_t h);
 int check_frame(const rt_context* c, int32_t w, int32_t h, const rt_settings* st);
 int check_frame_args(const rt_context* c, int32_t w, int32_t h, const rt_settings* st, int32_t rank, int32_t world,
                      int32_t layout);

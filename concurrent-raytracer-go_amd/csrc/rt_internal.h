@@ -1,6 +1,6 @@
 // rt_internal.h — host-side interfaces between the C ABI (rt_api.cpp and the
 // files around rt_context.h), the kernels (rt_kernel.hip, rt_stream.hip,
-// rt_image_ops.hip, rt_wavefront.hip, rt_schedule.hip, rt_adaptive.hip), the
+// rt_image_ops.hip, rt_wavefront.hip, rt_schedule.hip, rt_adaptive.hip, rt_aov.hip), the
 // scene loader (scene_json.cpp), the BVH builder (bvh.cpp) and the output
 // writers (image_io.cpp).
 #pragma once
@@ -572,6 +572,24 @@ struct Geo {
   const DBVHNode* bvh;
   int32_t ns, nt, use_bvh, nb;
 };
+
+// ---- first-hit feature buffers (rt_aov.hip; rt_context_render_aov_async)
+// One lane per pixel of the W x H frame, image layout; every output may be null.
+struct AovParams {
+  Geo g;                       // use_bvh as KParams: 0 linear scan, 1 a tree of spheres, 2 a tree with leaves of cubes
+  const DMat* mats;
+  CamFrame cf;                 // the camera rays' frame (rt_camera_frame)
+  uint64_t seed_key;
+  int32_t W, H, spp;
+  int32_t stack_depth;         // entries per lane of a BVH stack (the tree's depth)
+  float* albedo;               // W*H*3
+  float* normal;               // W*H*3
+  float* depth;                // W*H
+  float* coverage;             // W*H
+  int32_t* object;             // W*H
+};
+int launch_aov(const AovParams& p, void* stream);
+int preload_aov_kernels();
 
 // ---------------------------------------------------------------- wavefront path
 // (rt_wavefront.hip: BVH scenes)

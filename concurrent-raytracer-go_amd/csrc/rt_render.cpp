@@ -769,6 +769,60 @@ int rt_context_render_cameras_async(rt_context* c, int32_t w, int32_t h, const r
   return leave_stream(c, s);
 }
 
+// First-hit feature buffers (include/rt_api.h): one launch of
+// rt_aov.hip's kernel over the whole frame, timed like a render (ev0 .. ev1) and
+// ordered behind the context's last launch, but with no schedule, no counts in
+// the statistics and no state of a progression touched.
+int rt_context_render_aov_async(rt_context* c, int32_t w, int32_t h, const rt_settings* st, const rt_camera* camera,
+                                const rt_aov_buffers* out, void* stream) {
+  if (!c || !st || !out) {
+    set_error("rt_context_render_aov_async: context, settings or out is NULL");
+    return RT_E_INVALID;
+  }
+  if (!out->d_albedo && !out->d_normal && !out->d_depth && !out->d_coverage && !out->d_object) {
+    set_error("rt_context_render_aov_async: every buffer of out is NULL");
+    return RT_E_INVALID;
+  }
+  if (!c->have_scene) {
+    set_error("context has no scene");
+    return RT_E_INVALID;
+  }
+  if (st->samples < 1) {
+    set_error("rt_context_render_aov_async: samples must be at least 1");
+    return RT_E_INVALID;
+  }
+  int rc = check_settings(st, w, h);
+  if (rc) return rc;
+  AovParams p;
+  memset(&p, 0, sizeof p);
+  // (the caller's camera is read here and not again)
+  rc = camera_frame(camera ? *camera : c->flat.camera, st->camera, w, h, &p.cf);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const FlatScene& f = c->flat;
+  const int32_t use_bvh = f.bvh.empty() ? 0 : (bvh_has_cubes(f) ? 2 : 1);
+  p.g = Geo{c->d_spheres, c->d_tris, c->d_boxes, c->d_bvh, (int32_t)f.spheres.size(), (int32_t)f.tris.size(), use_bvh,
+            (int32_t)f.boxes.size()};
+  p.mats = c->d_mats;
+  p.seed_key = rt_rng_seed_key(st->seed);
+  p.W = w;
+  p.H = h;
+  p.spp = st->samples;
+  p.stack_depth = std::max(1, f.bvh_depth);
+  p.albedo = out->d_albedo;
+  p.normal = out->d_normal;
+  p.depth = out->d_depth;
+  p.coverage = out->d_coverage;
+  p.object = out->d_object;
+  hipStream_t s = (hipStream_t)stream;
+  rc = enter_stream(c, s);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  const int e = launch_aov(p, s);
+  if (e != hipSuccess) return launch_failed("feature buffers", e);
+  return leave_stream(c, s);
+}
+
 // rt_camera_orbit (include/rt_api.h states the formula and its order)
 int rt_camera_orbit(const rt_camera* cam, int32_t n, double degrees, rt_camera* out) {
   if (!cam || !out || n < 1) {

@@ -210,6 +210,21 @@ class Adaptive(ctypes.Structure):
     ]
 
 
+class AovBuffers(ctypes.Structure):
+    """rt_aov_buffers: the device pointers of a feature-buffer pass (None / 0: not written)."""
+
+    _fields_ = [
+        ("d_albedo", ctypes.c_void_p),
+        ("d_normal", ctypes.c_void_p),
+        ("d_depth", ctypes.c_void_p),
+        ("d_coverage", ctypes.c_void_p),
+        ("d_object", ctypes.c_void_p),
+    ]
+
+
+AOV_NAMES = ["albedo", "normal", "depth", "coverage", "object"]
+
+
 class Counts(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in COUNT_FIELDS] + [("culled", ctypes.c_uint64 * 9),
                                                                ("soft_occlusion", ctypes.c_uint64 * 9),
@@ -320,6 +335,7 @@ EXPORTED_SYMBOLS = [
     "rt_camera_orbit",
     "rt_stream_decode",
     "rt_soft_screen",
+    "rt_context_render_aov_async",
 ]
 
 _lib = None
@@ -444,6 +460,8 @@ def lib():
         "rt_stream_decode": (ctypes.c_int, [i32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                              ctypes.POINTER(ctypes.c_uint32), sz, ctypes.POINTER(ctypes.c_uint32)]),
         "rt_soft_screen": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 7 + [sz, ctypes.POINTER(i32)]),
+        "rt_context_render_aov_async": (ctypes.c_int, [vp, i32, i32, ctypes.POINTER(Settings), ctypes.POINTER(Camera),
+                                                       ctypes.POINTER(AovBuffers), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -869,6 +887,44 @@ class ParallelRenderer:
         }
         return img
 
+    def render_aov(self, scene: Scene, width: int, height: int, camera=None) -> dict:
+        """The first-hit feature buffers of the frame (rt_context_render_aov_async) with the
+        renderer's samples, seed and camera model, as numpy arrays: ``albedo`` and ``normal`` (H, W, 3)
+        float32, ``depth`` and ``coverage`` (H, W) float32, ``object`` (H, W) int32 (-1: nothing hit; depth
+        +Inf there).  camera: a Camera or a scene-file camera dict (with ``position``) in place of the
+        scene's.  Runs on the renderer's first device whatever ``num_devices`` is."""
+        if int(width) < 1 or int(height) < 1:
+            raise RenderError(f"render_aov: invalid image size {width}x{height}")
+        if int(self.settings.samples) < 1:
+            raise RenderError("render_aov: settings.samples must be >= 1")
+        if isinstance(camera, dict) and "position" not in camera:
+            raise RenderError("render_aov: a camera dict needs a position")
+        if camera is not None and not isinstance(camera, (dict, Camera, Scene)):
+            raise RenderError("render_aov: camera is a Camera, a Scene, a camera dict or None")
+        view = SceneView.from_buffer_copy(scene.view)  # (validated with the camera the pass shoots from)
+        if camera is not None:
+            view.camera = _as_camera(camera)
+        _check(lib().rt_validate(ctypes.byref(view), width, height, ctypes.byref(self.settings)))
+        import torch
+
+        dev = self.devices[0] if self.devices else 0
+        if self._prog_ctx is None:  # (the context render_progressive uses, kept like the rt_renderer)
+            self._prog_ctx = Context(dev)
+        ctx = self._prog_ctx
+        if self._tuning is not None:
+            ctx.set_tuning(self._tuning)
+        ctx.set_scene(scene)
+        npix = width * height
+        with torch.cuda.device(dev):
+            bufs = {n: torch.zeros(npix * (3 if n in ("albedo", "normal") else 1),
+                                   dtype=torch.int32 if n == "object" else torch.float32, device="cuda")
+                    for n in AOV_NAMES}
+            out = AovBuffers(*[bufs[n].data_ptr() for n in AOV_NAMES])
+            ctx.render_aov_async(width, height, self.settings, out, camera=camera, stream=0)
+            torch.cuda.synchronize()
+            return {n: bufs[n].cpu().numpy().reshape((height, width, 3) if n in ("albedo", "normal")
+                                                     else (height, width)) for n in AOV_NAMES}
+
     def rank_seconds(self) -> list:
         """Device seconds of each rank's render launches in the last render (load balance)."""
         r = self._renderer()
@@ -954,6 +1010,15 @@ class Context:
         rp = (ctypes.c_void_p * max(1, n))(*d_rgba) if d_rgba is not None else None
         _check(lib().rt_context_render_cameras_async(self._h, width, height, ctypes.byref(settings), n, cams, sd, rank,
                                                       world, layout, lp, rp, ctypes.c_void_p(stream)))
+
+    def render_aov_async(self, width, height, settings: Settings, out: AovBuffers, camera=None, stream: int = 0):
+        """rt_context_render_aov_async: the first-hit feature buffers of the whole frame
+        into the device buffers of ``out`` (an AovBuffers; a pointer of None / 0 is not written): albedo and
+        normal W*H*3 float32, depth and coverage W*H float32, object W*H int32.  camera: a Camera, a Scene or
+        a scene-file camera dict; None: the scene's.  No image is rendered and no state of the context changes."""
+        cam = ctypes.byref(_as_camera(camera)) if camera is not None else None
+        _check(lib().rt_context_render_aov_async(self._h, width, height, ctypes.byref(settings), cam, ctypes.byref(out),
+                                                  ctypes.c_void_p(stream)))
 
     def progressive_begin(self, width, height, settings: Settings, rank: int = 0, world: int = 1,
                           layout: int = RT_LAYOUT_IMAGE):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -517,6 +517,67 @@ int rt_context_render_cameras_async(rt_context* ctx, int32_t width, int32_t heig
  * is copied, and out[0] is cam bit for bit.  RT_E_INVALID for n < 1, a field
  * or degrees that is not finite, and a zero up. */
 int rt_camera_orbit(const rt_camera* cam, int32_t n, double degrees, rt_camera* out /* n */);
+
+/* First-hit feature buffers: what a denoiser, object picking
+ * and a depth or matte pass start from -- per pixel, the albedo, normal, depth,
+ * coverage and object of the camera rays' first hits.  No image is rendered.
+ *
+ * The definition.  For a width x height (W x H) image and n = settings->samples
+ * >= 1, sample s of pixel (x, y) has the render's own camera ray: its stream is
+ * rt_rng_init(key, y * W + x, s) (include/rt_rng.h, key = rt_rng_seed_key(
+ * settings->seed)), u = (x + draw0) / W, v = (y + draw1) / H, and its direction
+ * is ((lower_left + horizontal * u) + vertical * v) - origin per component, not
+ * normalised, from the frame of rt_camera_frame for the camera and the model
+ * (settings->camera) in use.  The sample's hit is hitWorld(ray, 0.001, +Inf)
+ * (renderer.go:333-346): the closest hittable, an exact tie going to the later
+ * one.  Its HitRecord is the reference's (sphere.go:42-58, triangle.go:67-81):
+ * T the ray parameter, Normal already turned against the ray; the material's
+ * GetAlbedo() is the JSON colour, except (1, 1, 1) for dielectric and (0, 0, 0)
+ * for diffuselight.  Per pixel, over the hitting samples in ascending s, with
+ * binary64 sums sumA (albedo), sumN (normal), sumT and the integer `hits`:
+ *   albedo    float3   (float)(sumA / n) per component (a miss adds black, as it does to the image)
+ *   normal    float3   (float)(sumN / n), not renormalised
+ *   depth     float    (float)(sumT / hits), +Inf when hits == 0
+ *   coverage  float    (float)((double)hits / n)
+ *   object    int32    the hittable index (the rt_object's index, a cube counts as one) of the
+ *                      lowest hitting s, -1 when hits == 0
+ * Divisions are plain IEEE binary64.  Pixel (x, y) is at y * W + x, row 0 the
+ * BOTTOM of the viewport like the image.  In both camera models the view-axis
+ * component of the direction is exactly the focal length 1, so T is the hit's
+ * distance ALONG THE VIEW AXIS in world units: `depth` is a z-buffer, not a
+ * distance from the eye.
+ * The buffers depend on the scene, the size, the camera, the camera model,
+ * samples and seed only: max_depth (0 included), recursive_reflections,
+ * soft_shadows, sky and every rt_tuning field change no bit of them, nor does
+ * force_bvh (the tree and the linear scan find the same hit).  A scene that
+ * rt_context_set_scene accepts with non-finite sphere geometry does not fault;
+ * the values at such hits carry no contract.
+ *
+ * The call.  Every pointer of rt_aov_buffers is a DEVICE pointer or NULL (that
+ * buffer is not written).  Asynchronous on `hip_stream` like the render calls.
+ * It covers the WHOLE frame in image layout: there are no rank / world shares
+ * and no packed layout -- the pass is a small fraction of a render, one device
+ * does it, and multi-device callers run it on their first device.  camera NULL:
+ * the scene's; else it is copied before the call returns.  A progression and
+ * the context's work schedules are not disturbed, a render after the call is
+ * byte for byte the render before it, and nothing counts in rt_context_stats;
+ * the call records HIP events around its own launch, so
+ * rt_context_last_kernel_seconds reports its device time when it was the last
+ * launch.
+ * RT_E_INVALID with a message, nothing enqueued and no buffer touched: a NULL
+ * ctx, settings or out; all five pointers NULL; no scene set; samples < 1; a
+ * size or samples range that rt_validate refuses; in look-at mode a camera
+ * that rt_camera_frame refuses. */
+typedef struct {
+  float* d_albedo;    /* W*H*3 */
+  float* d_normal;    /* W*H*3 */
+  float* d_depth;     /* W*H   */
+  float* d_coverage;  /* W*H   */
+  int32_t* d_object;  /* W*H   */
+} rt_aov_buffers;
+int rt_context_render_aov_async(rt_context* ctx, int32_t width, int32_t height, const rt_settings* settings,
+                                const rt_camera* camera /* NULL: the scene's */, const rt_aov_buffers* out,
+                                void* hip_stream);
 
 /* Progressive rendering: one frame's samples rendered over
  * several calls, with the image of the samples so far after each.  A context
