@@ -7,6 +7,7 @@
 //             [--pass-samples N [--time-budget SECONDS] [--converge PIXELS]
 //              [--adaptive TOL[,PATIENCE[,MIN]]] [--count-map FILE]]
 //             [--orbit N[,DEGREES]] [--aov PREFIX]
+//             [--denoise default|LEVELS[,SIGMA_COLOR[,SIGMA_DEPTH[,NORMAL_POWER]]]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -45,6 +46,16 @@
 //   object    the bytes 0..2 of (index + 1) * 2654435761 mod 2^32, each with its top bit set; a miss black
 // A size without pixels (a width or height <= 0) writes none.  Without --aov
 // nothing changes.
+// --denoise SPEC (one view, --samples >= 1, a size with
+// pixels) writes the DENOISED image instead of the raw one: the frame's linear
+// radiance is uploaded to device 0, where its first-hit feature buffers (the
+// render's size, seed and camera model; its samples, or those of the first
+// pass with --pass-samples) steer the à-trous filter (rt_denoise_async) whose
+// tone-mapped output is the image saved -- the plain render's, or the last
+// image of a progression (whose "pixels changed" lines and stop rules still
+// read the raw images).  SPEC is `default` (rt_denoise_default) or up to four
+// comma-separated fields that replace the defaults from the left.  It combines
+// with --aov and is refused with --orbit.
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
@@ -182,11 +193,13 @@ static void save_benchmark(const std::string& out_path, long long w, long long h
 // converge < 0: that rule is off.  adapt (--adaptive; null:
 // off): every pixel stops on its own, the progression also ends when none is
 // active; *mean_samples is the mean samples per pixel, and count_map (when
-// not empty) receives the counts as a grey PNG, count * 255 / cap.
+// not empty) receives the counts as a grey PNG, count * 255 / cap.  linear
+// (host, w*h*3 floats; null: not wanted) receives the last image's linear
+// radiance (--denoise).
 static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int pass_samples,
                               double budget_s, long long converge, const rt_adaptive* adapt,
                               const std::string& count_map, uint8_t* rgba, rt_stats* stats, int* rendered,
-                              double* mean_samples) {
+                              double* mean_samples, float* linear) {
   const auto t_new = std::chrono::steady_clock::now();
   rt_context* ctx = nullptr;
   if (rt_context_create(0, &ctx) != RT_OK) return RT_E_DEVICE;
@@ -195,6 +208,7 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
   const size_t npix = (size_t)w * (size_t)h;
   uint8_t* d_img[2] = {nullptr, nullptr};
   uint32_t* d_delta = nullptr;
+  float* d_lin = nullptr;
   int rc = rt_context_set_scene(ctx, scene, 0);
   stats->scene_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   auto hip_ok = [&](hipError_t e, const char* what) {
@@ -209,12 +223,13 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
   if (rc == RT_OK && hip_ok(hipMalloc((void**)&d_img[0], npix * 4), "hipMalloc") &&
       hip_ok(hipMalloc((void**)&d_img[1], npix * 4), "hipMalloc"))
     hip_ok(hipMalloc((void**)&d_delta, 2 * sizeof(uint32_t)), "hipMalloc");
+  if (rc == RT_OK && linear) hip_ok(hipMalloc((void**)&d_lin, npix * 3 * sizeof(float)), "hipMalloc");
   int done = 0, k = 0;
   double kernel_s = 0;
   while (rc == RT_OK) {
     const int n = std::min(pass_samples, st.samples - done);
     uint8_t* cur = d_img[k & 1];
-    rc = rt_context_progressive_add_async(ctx, n, nullptr, cur, nullptr);
+    rc = rt_context_progressive_add_async(ctx, n, d_lin, cur, nullptr);
     if (rc != RT_OK) break;
     uint32_t delta[2] = {0, 0};
     if (k > 0) {  // how much the preview still moved in this pass
@@ -244,6 +259,8 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
   }
   if (rc == RT_OK && k > 0)
     hip_ok(hipMemcpy(rgba, d_img[(k - 1) & 1], npix * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+  if (rc == RT_OK && k > 0 && linear)
+    hip_ok(hipMemcpy(linear, d_lin, npix * 3 * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
   if (rc == RT_OK) rc = rt_context_progressive_state(ctx, state);
   if (rc == RT_OK) *mean_samples = state[0] > 0 ? (double)state[2] / (double)state[0] : 0.0;
   if (rc == RT_OK && !count_map.empty()) {
@@ -267,7 +284,7 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
   const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   (void)rt_context_progressive_end(ctx);
-  for (void* p : {(void*)d_img[0], (void*)d_img[1], (void*)d_delta})
+  for (void* p : {(void*)d_img[0], (void*)d_img[1], (void*)d_delta, (void*)d_lin})
     if (p) (void)hipFree(p);
   rt_context_destroy(ctx);
   if (rc != RT_OK) {
@@ -433,8 +450,88 @@ static int write_aov(const rt_scene* scene, int32_t w, int32_t h, const rt_setti
   return RT_OK;
 }
 
+// --denoise: the à-trous filter (rt_denoise_async) over the
+// frame's linear radiance `linear` (host, w*h*3) on device 0: the first-hit
+// feature buffers of the frame with feature_samples samples (st's seed and
+// camera model), then the filter; rgba (host, w*h*4) receives its tone-mapped
+// output.
+static int denoise_image(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int feature_samples,
+                         const rt_denoise& dn, const float* linear, uint8_t* rgba) {
+  const size_t npix = (size_t)w * (size_t)h;
+  rt_context* ctx = nullptr;
+  int rc = rt_context_create(0, &ctx);
+  if (rc != RT_OK) return rc;
+  rc = rt_context_set_scene(ctx, scene, 0);
+  // one device block: color | albedo | normal | depth | object, then the image and the workspace
+  float* d = nullptr;
+  uint8_t* d_rgba = nullptr;
+  void* d_work = nullptr;
+  const size_t work_bytes = rt_denoise_workspace_bytes(w, h);
+  auto hip_ok = [&](hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    fprintf(stderr, "%s failed: %s\n", what, hipGetErrorString(e));
+    rc = RT_E_DEVICE;
+    return false;
+  };
+  if (rc == RT_OK && hip_ok(hipMalloc((void**)&d, npix * 11 * sizeof(float)), "hipMalloc") &&
+      hip_ok(hipMalloc((void**)&d_rgba, npix * 4), "hipMalloc") && hip_ok(hipMalloc(&d_work, work_bytes), "hipMalloc"))
+    hip_ok(hipMemcpy(d, linear, npix * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
+  if (rc == RT_OK) {
+    rt_settings fst = st;
+    fst.samples = feature_samples;
+    const rt_aov_buffers out = {d + npix * 3, d + npix * 6, d + npix * 9, nullptr, (int32_t*)(d + npix * 10)};
+    rc = rt_context_render_aov_async(ctx, w, h, &fst, nullptr, &out, nullptr);
+  }
+  if (rc == RT_OK) {
+    const rt_denoise_inputs in = {d, d + npix * 6, d + npix * 9, d + npix * 3, (const int32_t*)(d + npix * 10)};
+    rc = rt_denoise_async(&dn, w, h, &in, nullptr, d_rgba, d_work, work_bytes, nullptr);
+  }
+  if (rc == RT_OK) hip_ok(hipMemcpy(rgba, d_rgba, npix * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+  const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
+  for (void* p : {(void*)d, (void*)d_rgba, d_work})
+    if (p) (void)hipFree(p);
+  rt_context_destroy(ctx);
+  if (rc != RT_OK && !err.empty()) fprintf(stderr, "%s\n", err.c_str());
+  return rc;
+}
+
+// --denoise SPEC: `default`, or LEVELS[,SIGMA_COLOR[,SIGMA_DEPTH[,NORMAL_POWER]]] over the defaults
+// within rt_denoise's ranges (include/rt_api.h), checked before anything is rendered
+static bool denoise_in_range(const rt_denoise& d) {
+  const int32_t np = d.normal_power;
+  return d.levels >= 1 && d.levels <= 8 && np >= 0 && np <= 128 && (np & (np - 1)) == 0 && std::isfinite(d.sigma_color) &&
+         d.sigma_color >= 0 && std::isfinite(d.sigma_depth) && d.sigma_depth >= 0;
+}
+static bool parse_denoise(const std::string& x, rt_denoise* dn) {
+  rt_denoise_default(dn);
+  if (x == "default") return true;
+  if (x.empty()) return false;
+  size_t pos = 0;
+  for (int nf = 0;; ++nf) {
+    if (nf == 4) return false;  // a fifth field
+    const size_t c = x.find(',', pos);
+    const std::string part = x.substr(pos, c == std::string::npos ? std::string::npos : c - pos);
+    long long v = 0;
+    if (nf == 0 || nf == 3) {
+      if (!parse_int(part.c_str(), &v) || v < -1000 || v > 1000) return false;
+      (nf == 0 ? dn->levels : dn->normal_power) = (int32_t)v;
+    } else {
+      char* end = nullptr;
+      errno = 0;
+      const double f = strtod(part.c_str(), &end);
+      if (part.empty() || !end || *end || errno != 0) return false;
+      (nf == 1 ? dn->sigma_color : dn->sigma_depth) = f;
+    }
+    if (c == std::string::npos) return true;
+    pos = c + 1;
+  }
+}
+
 int main(int argc, char** argv) {
   std::vector<std::string> args;
+  bool denoise_on = false;     // --denoise SPEC
+  rt_denoise dn;
+  rt_denoise_default(&dn);
   std::string aov_prefix;      // --aov PREFIX (empty: no feature buffers)
   long long orbit_n = 0;       // --orbit N[,DEGREES] (0: one render)
   double orbit_deg = 360.0;
@@ -550,6 +647,14 @@ int main(int argc, char** argv) {
         fprintf(stderr, "invalid --aov (a file name prefix)\n");
         return 2;
       }
+    } else if (a == "--denoise") {  // write the à-trous-filtered image
+      const std::string x = need("--denoise");
+      if (!parse_denoise(x, &dn) || !denoise_in_range(dn)) {
+        fprintf(stderr, "invalid --denoise %s (default, or LEVELS[,SIGMA_COLOR[,SIGMA_DEPTH[,NORMAL_POWER]]]: 1..8, "
+                        ">= 0, >= 0, 0 or a power of two <= 128)\n", x.c_str());
+        return 2;
+      }
+      denoise_on = true;
     } else if (a == "--sky") {  // opt-in sky on miss (atmosphere.go presets); default: black
       const std::string k = need("--sky");
       if (k == "none") st.sky = RT_SKY_NONE;
@@ -579,6 +684,10 @@ int main(int argc, char** argv) {
   }
   if (!aov_prefix.empty() && (orbit_n > 0 || st.samples < 1)) {
     fprintf(stderr, "--aov needs --samples >= 1 and one view (not with --orbit)\n");
+    return 2;
+  }
+  if (denoise_on && (orbit_n > 0 || st.samples < 1)) {
+    fprintf(stderr, "--denoise needs --samples >= 1 and one view (not with --orbit)\n");
     return 2;
   }
   if (pass_samples > 0 && st.num_devices > 1) {
@@ -616,6 +725,10 @@ int main(int argc, char** argv) {
   if (!parse_int(args[3].c_str(), &h)) {
     printf("Invalid height: %s\n", args[3].c_str());
     return 1;
+  }
+  if (denoise_on && (w <= 0 || h <= 0)) {
+    fprintf(stderr, "--denoise needs a size with pixels (%lldx%lld)\n", w, h);
+    return 2;
   }
   printf("Loading scene from: %s\n", scene_file.c_str());
   rt_scene_buf* sb = nullptr;
@@ -670,6 +783,12 @@ int main(int argc, char** argv) {
     rt_scene_free(sb);
     return 0;
   }
+  // (--denoise holds the frame's linear image on the host: sized only for a frame that will render)
+  if (denoise_on && (w > 65536 || h > 65536 || rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK)) {
+    fprintf(stderr, "render failed: %s\n", w > 65536 || h > 65536 ? "invalid image size" : rt_last_error());
+    rt_scene_free(sb);
+    return 2;
+  }
   if (orbit_n > 0) {
     printf("Rendering at %lldx%lld resolution...\n", w, h);
     fflush(stdout);
@@ -720,11 +839,20 @@ int main(int argc, char** argv) {
     memset(&stats, 0, sizeof stats);
     int rendered = 0;
     double mean_samples = -1;
+    std::vector<float> linear(denoise_on ? (size_t)w * (size_t)h * 3 : 0);
     if (rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK ||
         render_progressive(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)pass_samples, budget_s, converge,
                            adaptive_on ? &adapt : nullptr, count_map, rgba.data(), &stats, &rendered,
-                           &mean_samples) != RT_OK) {
+                           &mean_samples, denoise_on ? linear.data() : nullptr) != RT_OK) {
       fprintf(stderr, "render failed: %s\n", rt_last_error());
+      rt_scene_free(sb);
+      return 2;
+    }
+    // (the features of the first pass's samples, as ParallelRenderer.render_progressive takes them)
+    if (denoise_on && denoise_image(rt_scene_view(sb), (int32_t)w, (int32_t)h, st,
+                                    (int)std::min<long long>(st.samples, pass_samples), dn, linear.data(),
+                                    rgba.data()) != RT_OK) {
+      fprintf(stderr, "denoise failed: %s\n", rt_last_error());
       rt_scene_free(sb);
       return 2;
     }
@@ -774,9 +902,18 @@ int main(int argc, char** argv) {
   memset(&stats, 0, sizeof stats);
   // img := renderer.Render(scene, width, height) (main.go:51): timed by
   // Render itself (renderer.go:68,101: stats.render_seconds)
-  int rc = rt_renderer_render(rr, scene, (int32_t)w, (int32_t)h, &st, nullptr, rgba.data(), &stats);
+  std::vector<float> linear(denoise_on ? npix * 3 : 0);
+  int rc = rt_renderer_render(rr, scene, (int32_t)w, (int32_t)h, &st, denoise_on ? linear.data() : nullptr, rgba.data(),
+                              &stats);
   if (rc != RT_OK) {
     fprintf(stderr, "render failed: %s\n", rt_last_error());
+    rt_renderer_destroy(rr);
+    rt_scene_free(sb);
+    return 2;
+  }
+  if (denoise_on &&
+      denoise_image(scene, (int32_t)w, (int32_t)h, st, st.samples, dn, linear.data(), rgba.data()) != RT_OK) {
+    fprintf(stderr, "denoise failed: %s\n", rt_last_error());
     rt_renderer_destroy(rr);
     rt_scene_free(sb);
     return 2;

@@ -1,6 +1,6 @@
 // rt_internal.h — host-side interfaces between the C ABI (rt_api.cpp and the
 // files around rt_context.h), the kernels (rt_kernel.hip, rt_stream.hip,
-// rt_image_ops.hip, rt_wavefront.hip, rt_schedule.hip, rt_adaptive.hip, rt_aov.hip), the
+// rt_image_ops.hip, rt_wavefront.hip, rt_schedule.hip, rt_adaptive.hip, rt_aov.hip, rt_denoise.hip), the
 // scene loader (scene_json.cpp), the BVH builder (bvh.cpp) and the output
 // writers (image_io.cpp).
 #pragma once
@@ -590,6 +590,27 @@ struct AovParams {
 };
 int launch_aov(const AovParams& p, void* stream);
 int preload_aov_kernels();
+
+// ---- à-trous denoiser (rt_denoise.hip; rt_denoise_async)
+// Checked arguments of one call: image layout, device pointers.  The workspace
+// holds three 16-byte records per pixel (two colour buffers that ping-pong and
+// the guide buffer, include/rt_denoise.h), 256-byte aligned by the launcher.
+constexpr size_t kDenoiseRecordBytes = 48;  // per pixel
+constexpr size_t kDenoiseAlign = 256;
+struct DenoiseParams {
+  rt_denoise dn;               // checked (rt_denoise_check)
+  int32_t W, H;
+  const float* color;          // W*H*3
+  const float* normal;         // W*H*3
+  const float* depth;          // W*H
+  const float* albedo;         // W*H*3, or null: no demodulation (also when dn.demodulate is 0)
+  const int32_t* object;       // W*H, or null
+  float* out_linear;           // W*H*3 (may be color), or null
+  uint8_t* out_rgba;           // W*H*4, or null
+  void* workspace;             // at least kDenoiseRecordBytes * W * H + kDenoiseAlign bytes
+};
+int launch_denoise(const DenoiseParams& p, void* stream);
+int preload_denoise_kernels();
 
 // ---------------------------------------------------------------- wavefront path
 // (rt_wavefront.hip: BVH scenes)

@@ -225,6 +225,31 @@ class AovBuffers(ctypes.Structure):
 AOV_NAMES = ["albedo", "normal", "depth", "coverage", "object"]
 
 
+class Denoise(ctypes.Structure):
+    """rt_denoise: the parameters of the à-trous denoiser (default_denoise())."""
+
+    _fields_ = [
+        ("levels", ctypes.c_int32),
+        ("normal_power", ctypes.c_int32),
+        ("sigma_color", ctypes.c_double),
+        ("sigma_depth", ctypes.c_double),
+        ("demodulate", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+    ]
+
+
+class DenoiseInputs(ctypes.Structure):
+    """rt_denoise_inputs: color, normal and depth are required; albedo and object may be None / 0."""
+
+    _fields_ = [
+        ("color", ctypes.c_void_p),
+        ("normal", ctypes.c_void_p),
+        ("depth", ctypes.c_void_p),
+        ("albedo", ctypes.c_void_p),
+        ("object", ctypes.c_void_p),
+    ]
+
+
 class Counts(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in COUNT_FIELDS] + [("culled", ctypes.c_uint64 * 9),
                                                                ("soft_occlusion", ctypes.c_uint64 * 9),
@@ -336,6 +361,10 @@ EXPORTED_SYMBOLS = [
     "rt_stream_decode",
     "rt_soft_screen",
     "rt_context_render_aov_async",
+    "rt_denoise_default",
+    "rt_denoise_workspace_bytes",
+    "rt_denoise_async",
+    "rt_denoise_host",
 ]
 
 _lib = None
@@ -462,6 +491,11 @@ def lib():
         "rt_soft_screen": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 7 + [sz, ctypes.POINTER(i32)]),
         "rt_context_render_aov_async": (ctypes.c_int, [vp, i32, i32, ctypes.POINTER(Settings), ctypes.POINTER(Camera),
                                                        ctypes.POINTER(AovBuffers), vp]),
+        "rt_denoise_default": (None, [ctypes.POINTER(Denoise)]),
+        "rt_denoise_workspace_bytes": (sz, [i32, i32]),
+        "rt_denoise_async": (ctypes.c_int, [ctypes.POINTER(Denoise), i32, i32, ctypes.POINTER(DenoiseInputs), vp, vp,
+                                             vp, sz, vp]),
+        "rt_denoise_host": (ctypes.c_int, [ctypes.POINTER(Denoise), i32, i32, ctypes.POINTER(DenoiseInputs), vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -613,6 +647,7 @@ class ParallelRenderer:
         self._prog_ctx = None  # its Context (made by the first call, kept)
         self.last_sample_counts = None  # per-pixel samples of the last render_progressive (H x W)
         self.last_progressive_state = None  # Context.progressive_state() at its end
+        self.last_denoised_linear = None  # the filter's linear output of the last denoised render (H x W x 3)
 
     def set_tuning(self, tuning: Tuning):
         self._tuning = tuning
@@ -740,7 +775,7 @@ class ParallelRenderer:
         return rgba
 
     def render_progressive(self, scene: Scene, width: int, height: int, pass_samples: int, time_budget=None,
-                           until_changed_pixels=None, on_pass=None, adaptive=None) -> np.ndarray:
+                           until_changed_pixels=None, on_pass=None, adaptive=None, denoise=None) -> np.ndarray:
         """Render the frame ``pass_samples`` samples at a time, on one device.
 
         ``self.settings.samples`` is the cap; the last pass is clipped to it.
@@ -761,6 +796,13 @@ class ParallelRenderer:
         of ``render`` with samples = ``last_sample_counts[p]``.  In every mode
         ``last_sample_counts`` (H x W uint32) and ``last_progressive_state``
         (Context.progressive_state) are set.
+
+        ``denoise``: None, or the filter's parameters (a Denoise, a dict of its fields,
+        True for the defaults).  The first-hit feature buffers are rendered once before the first pass,
+        with min(cap, pass_samples) samples; every pass's image is then denoised, ``on_pass`` receives the
+        denoised preview and the denoised last image is returned, its linear radiance in
+        ``last_denoised_linear``.  ``changed_pixels`` and every stop rule still read the raw images, and
+        ``last_linear`` and ``last_sample_counts`` stay those of the raw progression.
         """
         t0 = time.perf_counter()
         if (len(self.devices) if self.devices else max(1, self.settings.num_devices)) > 1:
@@ -769,6 +811,7 @@ class ParallelRenderer:
         if pass_samples < 1 or cap < 1:
             raise RenderError("render_progressive: pass_samples and settings.samples must be >= 1")
         _check(lib().rt_validate(ctypes.byref(scene.view), width, height, ctypes.byref(self.settings)))
+        dn = _as_denoise(denoise) if denoise is not None else None
         import torch
 
         dev = self.devices[0] if self.devices else 0
@@ -784,6 +827,13 @@ class ParallelRenderer:
             bufs = [torch.zeros(npix * 4, dtype=torch.uint8, device="cuda") for _ in range(2)]
             delta = torch.zeros(2, dtype=torch.int32, device="cuda")
             counts = torch.zeros(npix, dtype=torch.int32, device="cuda")
+            if dn is not None:  # the feature buffers, once: the first pass's samples of the same frame
+                feat, work, nbytes, out_lin, out_rgba = self._denoise_buffers(npix, width, height)
+                fst = Settings.from_buffer_copy(self.settings)
+                fst.samples = min(cap, int(pass_samples))
+                ctx.render_aov_async(width, height, fst,
+                                     AovBuffers(feat["albedo"].data_ptr(), feat["normal"].data_ptr(),
+                                                feat["depth"].data_ptr(), None, feat["object"].data_ptr()), stream=0)
             ctx.progressive_begin(width, height, self.settings)
             if adaptive is not None:
                 ctx.progressive_set_adaptive(adaptive["tolerance"], adaptive.get("patience", 1),
@@ -796,9 +846,13 @@ class ParallelRenderer:
                     ctx.progressive_add(n, lin.data_ptr(), cur.data_ptr(), 0)
                     if k > 0:  # how much the preview still moved in this pass
                         rgba_delta_async(prev.data_ptr(), cur.data_ptr(), npix, delta.data_ptr(), 0)
+                    if dn is not None:  # (reads the raw image, writes buffers of its own)
+                        denoise_async(width, height, lin.data_ptr(), feat["normal"].data_ptr(),
+                                      feat["depth"].data_ptr(), feat["albedo"].data_ptr(), feat["object"].data_ptr(),
+                                      out_lin.data_ptr(), out_rgba.data_ptr(), work.data_ptr(), nbytes, dn, 0)
                     torch.cuda.synchronize()
                     done += n
-                    img = cur.cpu().numpy().reshape(height, width, 4)
+                    img = (out_rgba if dn is not None else cur).cpu().numpy().reshape(height, width, 4)
                     changed = int(delta[0].item()) & 0xFFFFFFFF if k > 0 else None
                     if on_pass is not None:
                         on_pass(done, img, changed)
@@ -819,6 +873,8 @@ class ParallelRenderer:
             finally:
                 ctx.progressive_end()
             self.last_linear = lin.cpu().numpy().reshape(height, width, 3)
+            if dn is not None:
+                self.last_denoised_linear = out_lin.cpu().numpy().reshape(height, width, 3)
             self.last_sample_counts = counts.cpu().numpy().view(np.uint32).reshape(height, width)
         self.last_progressive_state = state
         self.last_samples = done
@@ -924,6 +980,69 @@ class ParallelRenderer:
             torch.cuda.synchronize()
             return {n: bufs[n].cpu().numpy().reshape((height, width, 3) if n in ("albedo", "normal")
                                                      else (height, width)) for n in AOV_NAMES}
+
+    @staticmethod
+    def _denoise_buffers(npix: int, width: int, height: int):
+        """Device buffers of a denoised frame: the four feature buffers the filter reads, its workspace
+        and its two outputs (torch tensors on the current device)."""
+        import torch
+
+        feat = {n: torch.zeros(npix * (3 if n in ("albedo", "normal") else 1),
+                               dtype=torch.int32 if n == "object" else torch.float32, device="cuda")
+                for n in ("albedo", "normal", "depth", "object")}
+        nbytes = denoise_workspace_bytes(width, height)
+        work = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        out_lin = torch.zeros(npix * 3, dtype=torch.float32, device="cuda")
+        out_rgba = torch.zeros(npix * 4, dtype=torch.uint8, device="cuda")
+        return feat, work, nbytes, out_lin, out_rgba
+
+    def render_denoised(self, scene: Scene, width: int, height: int, params=None, camera=None) -> np.ndarray:
+        """Render, then denoise: the frame of ``render`` (the renderer's settings; camera as
+        in ``render_aov``), its first-hit feature buffers with the same samples, seed and camera model, and
+        rt_denoise_async over both, on the renderer's first device.  params: a Denoise, a dict of its fields
+        or None (default_denoise()).  Returns the denoised (H, W, 4) uint8 image; ``last_linear`` is the raw
+        render's linear radiance as after ``render``, ``last_denoised_linear`` the filter's."""
+        if int(width) < 1 or int(height) < 1:
+            raise RenderError(f"render_denoised: invalid image size {width}x{height}")
+        if int(self.settings.samples) < 1:
+            raise RenderError("render_denoised: settings.samples must be >= 1")
+        if isinstance(camera, dict) and "position" not in camera:
+            raise RenderError("render_denoised: a camera dict needs a position")
+        if camera is not None and not isinstance(camera, (dict, Camera, Scene)):
+            raise RenderError("render_denoised: camera is a Camera, a Scene, a camera dict or None")
+        dn = _as_denoise(params)
+        view = SceneView.from_buffer_copy(scene.view)  # (validated with the camera the frame is shot from)
+        if camera is not None:
+            view.camera = _as_camera(camera)
+        _check(lib().rt_validate(ctypes.byref(view), width, height, ctypes.byref(self.settings)))
+        import torch
+
+        dev = self.devices[0] if self.devices else 0
+        if self._prog_ctx is None:  # (the context render_progressive and render_aov use, kept)
+            self._prog_ctx = Context(dev)
+        ctx = self._prog_ctx
+        if self._tuning is not None:
+            ctx.set_tuning(self._tuning)
+        ctx.set_scene(scene)
+        npix = width * height
+        with torch.cuda.device(dev):
+            lin = torch.zeros(npix * 3, dtype=torch.float32, device="cuda")
+            feat, work, nbytes, out_lin, out_rgba = self._denoise_buffers(npix, width, height)
+            if camera is None:
+                ctx.render_async(width, height, self.settings, lin.data_ptr(), 0, 0)
+            else:
+                ctx.render_cameras_async(width, height, self.settings, [camera], [lin.data_ptr()], stream=0)
+            ctx.render_aov_async(width, height, self.settings,
+                                 AovBuffers(feat["albedo"].data_ptr(), feat["normal"].data_ptr(),
+                                            feat["depth"].data_ptr(), None, feat["object"].data_ptr()),
+                                 camera=camera, stream=0)
+            denoise_async(width, height, lin.data_ptr(), feat["normal"].data_ptr(), feat["depth"].data_ptr(),
+                          feat["albedo"].data_ptr(), feat["object"].data_ptr(), out_lin.data_ptr(),
+                          out_rgba.data_ptr(), work.data_ptr(), nbytes, dn, 0)
+            torch.cuda.synchronize()
+            self.last_linear = lin.cpu().numpy().reshape(height, width, 3)
+            self.last_denoised_linear = out_lin.cpu().numpy().reshape(height, width, 3)
+            return out_rgba.cpu().numpy().reshape(height, width, 4)
 
     def rank_seconds(self) -> list:
         """Device seconds of each rank's render launches in the last render (load balance)."""
@@ -1234,6 +1353,75 @@ def rgba_delta_async(d_a: int, d_b: int, npix: int, d_out: int, stream: int = 0)
     (pixels that differ) and d_out[1] (the largest byte difference); zeroes d_out first."""
     _check(lib().rt_rgba_delta_async(ctypes.c_void_p(d_a), ctypes.c_void_p(d_b), npix, ctypes.c_void_p(d_out),
                                      ctypes.c_void_p(stream)))
+
+
+def default_denoise(**over) -> Denoise:
+    """rt_denoise_default (levels 4, normal_power 32, sigma_color 0.5, sigma_depth 0.05, demodulate 1),
+    with the given fields replaced."""
+    d = Denoise()
+    lib().rt_denoise_default(ctypes.byref(d))
+    for k, v in over.items():
+        if k not in ("levels", "normal_power", "sigma_color", "sigma_depth", "demodulate"):
+            raise RenderError(f"default_denoise: no such field {k}")
+        setattr(d, k, v)
+    return d
+
+
+def _as_denoise(params) -> Denoise:
+    """None: the defaults; a Denoise as it is; a dict: default_denoise(**dict)."""
+    if params is None or params is True:
+        return default_denoise()
+    if isinstance(params, Denoise):
+        return params
+    if isinstance(params, dict):
+        return default_denoise(**params)
+    raise RenderError("denoise parameters are a Denoise, a dict of its fields or None")
+
+
+def denoise_workspace_bytes(width: int, height: int) -> int:
+    """rt_denoise_workspace_bytes: the device bytes rt_denoise_async needs for a width x height image."""
+    return int(lib().rt_denoise_workspace_bytes(width, height))
+
+
+def denoise_async(width: int, height: int, d_color: int, d_normal: int, d_depth: int, d_albedo=None, d_object=None,
+                  d_out_linear=None, d_out_rgba=None, d_workspace=None, workspace_bytes: int = 0, params=None,
+                  stream: int = 0):
+    """rt_denoise_async (DESIGN.md §4.13): every argument a device pointer (an int; None: not given);
+    asynchronous on ``stream``.  d_out_linear may be d_color (in place)."""
+    p = _as_denoise(params)
+    inp = DenoiseInputs(d_color, d_normal, d_depth, d_albedo, d_object)
+    _check(lib().rt_denoise_async(ctypes.byref(p), width, height, ctypes.byref(inp), ctypes.c_void_p(d_out_linear),
+                                  ctypes.c_void_p(d_out_rgba), ctypes.c_void_p(d_workspace), workspace_bytes,
+                                  ctypes.c_void_p(stream)))
+
+
+def denoise_host(color, normal, depth, albedo=None, object=None, params=None):
+    """rt_denoise_host: the denoiser on numpy arrays, without a device.  color, normal (and albedo) are
+    (H, W, 3) float32, depth (H, W) float32, object (H, W) int32.  Returns (linear (H, W, 3) float32,
+    rgba (H, W, 4) uint8)."""
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise RenderError("denoise_host: color is an (H, W, 3) array")
+    h, w = color.shape[:2]
+
+    def arr(a, dtype, shape, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape != shape:
+            raise RenderError(f"denoise_host: {name} has shape {a.shape}, expected {shape}")
+        return a
+
+    normal = arr(normal, np.float32, (h, w, 3), "normal")
+    depth = arr(depth, np.float32, (h, w), "depth")
+    albedo = arr(albedo, np.float32, (h, w, 3), "albedo")
+    obj = arr(object, np.int32, (h, w), "object")
+    p = _as_denoise(params)
+    inp = DenoiseInputs(*[a.ctypes.data if a is not None else None for a in (color, normal, depth, albedo, obj)])
+    lin = np.zeros((h, w, 3), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    _check(lib().rt_denoise_host(ctypes.byref(p), w, h, ctypes.byref(inp), lin.ctypes.data, rgba.ctypes.data))
+    return lin, rgba
 
 
 def max_local_tiles(width: int, height: int, world: int) -> int:

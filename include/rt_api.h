@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async, rt_denoise, rt_denoise_inputs, rt_denoise_default, rt_denoise_workspace_bytes, rt_denoise_async, rt_denoise_host); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -647,6 +647,100 @@ int rt_adaptive_step(const uint8_t old_rgba[4], const uint8_t new_rgba[4], int32
  * Exact and independent of order: a progression's stop criterion (how much
  * the preview still moved in the last pass). */
 int rt_rgba_delta_async(const uint8_t* d_a, const uint8_t* d_b, size_t npix, uint32_t* d_out, void* hip_stream);
+
+/* À-trous denoiser guided by the first-hit feature buffers:
+ * an edge-stopping wavelet filter over a render's linear image, steered by the
+ * buffers of rt_context_render_aov_async, so that a preview of a few samples
+ * per pixel can be shown without most of its Monte-Carlo noise.  The
+ * project's own feature (the reference has no denoiser), defined here to the
+ * bit: binary64 `+ - * /` and comparisons only, in a fixed order, so that the
+ * device kernels, rt_denoise_host and a restatement in any language agree
+ * exactly (include/rt_denoise.h is the code both sides run).
+ *
+ * Inputs, per pixel p = y * W + x, laid out as rt_context_render_async and
+ * rt_aov_buffers lay them out:
+ *   color   float3  required: the linear mean radiance (d_linear of any render)
+ *   normal  float3  required
+ *   depth   float   required
+ *   albedo  float3  optional (NULL: no demodulation)
+ *   object  int32   optional (NULL: no id stop)
+ * Coverage is not read.  valid(p) means depth[p] is finite (a miss has +Inf).
+ * Float inputs are widened to binary64 before use.
+ *
+ * Parameters (rt_denoise; rt_denoise_default sets the defaults):
+ *   levels        1..8                            default 4
+ *   normal_power  0 (off) or a power of two <= 128 default 32
+ *   sigma_color   >= 0, 0: off                    default 0.5
+ *   sigma_depth   >= 0, 0: off                    default 0.05
+ *   demodulate    0 or 1 (ignored when albedo is NULL)  default 1
+ * Anything else -- a NaN or infinite sigma included -- is RT_E_INVALID.
+ *
+ * Prepare.  amin = 2^-6 and floor(a) = a > amin ? a : amin.  With
+ * demodulation e_0(p)[k] = (float)((double)color[k] / floor((double)albedo[k]));
+ * without it e_0 = color.
+ *
+ * Level i = 0 .. levels - 1, with the step s = 2^i, sc = sigma_color * 2^-i
+ * (exact) and h = {3/8, 1/4, 1/16}.  For every valid p, sumw = 0 and
+ * sum[3] = 0 in binary64, then the taps in this order: dy = -2..2 in the outer
+ * loop, dx = -2..2 in the inner loop, q = (x + s * dx, y + s * dy).  A tap is
+ * skipped when q is outside the image, when q is not valid, or when object is
+ * given and object[q] != object[p].  Otherwise, in this order of operations:
+ *   1. w = h[|dx|] * h[|dy|]
+ *   2. if normal_power > 0: t = (nx_p * nx_q + ny_p * ny_q) + nz_p * nz_q,
+ *      t = t > 0 ? t : 0, t squared log2(normal_power) times, w = w * t
+ *   3. if sigma_depth > 0: r = (z_q - z_p) / (sigma_depth * z_p),
+ *      w = w / (1 + r * r)
+ *   4. if sigma_color > 0: D = e_i(q) - e_i(p), d2 = (D0 * D0 + D1 * D1) + D2 * D2,
+ *      w = w / (1 + d2 / (sc * sc))
+ *   5. sumw += w and sum[k] += w * e_i(q)[k]
+ * Then e_{i+1}(p)[k] = sumw > 0 ? (float)(sum[k] / sumw) : e_i(p)[k].  A pixel
+ * that is not valid keeps e_i(p).
+ *
+ * Output, with L = levels.  A valid p gets out[k] = (float)((double)e_L[k] *
+ * floor((double)albedo[k])) with demodulation and e_L without it; a pixel
+ * that is not valid gets color bit for bit.  out_rgba, if given, is
+ * rt_tonemap_rgba of out, byte for byte.  Either output may be NULL, but not
+ * both.  out_linear == color (in place) is allowed; any other overlap carries
+ * no contract.  No memory address depends on a pixel's value, so non-finite
+ * colours, zero normals and depth <= 0 cannot fault; their values carry no
+ * contract beyond the sumw > 0 rule.
+ *
+ * What it cannot do: first-hit features say nothing about what a mirror shows
+ * or where a shadow falls, so reflections on metal and shadow edges are
+ * blurred (DESIGN.md §4.13 has the figures); sigma_color and levels are the
+ * controls for it.
+ *
+ * rt_denoise_async takes no context, like rt_rgba_delta_async.  Every pointer
+ * of `in`, both outputs and the workspace are DEVICE pointers of the current
+ * device; the caller owns the workspace (rt_denoise_workspace_bytes(w, h)
+ * bytes at least, at most 64 * w * h + 256; 0 for a size rt_validate refuses),
+ * nothing is allocated, and the call is asynchronous on `hip_stream`.
+ * RT_E_INVALID with a message, nothing enqueued and no buffer touched: NULL
+ * params or inputs, a NULL required input, both outputs NULL, a size that
+ * rt_validate refuses, a NULL or too small workspace, parameters out of range.
+ * rt_denoise_host does the same with host pointers and no device. */
+typedef struct {
+  int32_t levels;
+  int32_t normal_power;
+  double sigma_color;
+  double sigma_depth;
+  int32_t demodulate;
+  int32_t _pad;
+} rt_denoise;
+typedef struct {
+  const float* color;     /* W*H*3, required */
+  const float* normal;    /* W*H*3, required */
+  const float* depth;     /* W*H,   required */
+  const float* albedo;    /* W*H*3 or NULL */
+  const int32_t* object;  /* W*H   or NULL */
+} rt_denoise_inputs;
+void rt_denoise_default(rt_denoise* d);
+size_t rt_denoise_workspace_bytes(int32_t width, int32_t height);
+int rt_denoise_async(const rt_denoise* params, int32_t width, int32_t height, const rt_denoise_inputs* in,
+                     float* d_out_linear, uint8_t* d_out_rgba, void* d_workspace, size_t workspace_bytes,
+                     void* hip_stream);
+int rt_denoise_host(const rt_denoise* params, int32_t width, int32_t height, const rt_denoise_inputs* in,
+                    float* out_linear, uint8_t* out_rgba);
 
 /* What a context has done so far (diagnostics): work schedules built (a new
  * scene, frame, rank or settings key; a measured re-cut counts too),
