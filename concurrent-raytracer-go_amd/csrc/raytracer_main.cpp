@@ -8,6 +8,7 @@
 //              [--adaptive TOL[,PATIENCE[,MIN]]] [--count-map FILE]]
 //             [--orbit N[,DEGREES]] [--aov PREFIX]
 //             [--denoise default|LEVELS[,SIGMA_COLOR[,SIGMA_DEPTH[,NORMAL_POWER]]]]
+//             [--temporal default|MAX_HISTORY[,DEPTH_TOL[,NORMAL_MIN]]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -55,7 +56,15 @@
 // image of a progression (whose "pixels changed" lines and stop rules still
 // read the raw images).  SPEC is `default` (rt_denoise_default) or up to four
 // comma-separated fields that replace the defaults from the left.  It combines
-// with --aov and is refused with --orbit.
+// with --aov and is refused with --orbit unless --temporal is given.
+// --temporal SPEC (only with --orbit, --samples >= 1) writes
+// the ACCUMULATED views to the files --orbit writes: view f is rendered with
+// seed --seed + f, gets a first-hit feature pass of its own, and
+// rt_temporal_async reprojects view f - 1's result into it and blends.  SPEC is
+// `default` (rt_temporal_default) or up to three comma-separated fields that
+// replace the defaults from the left.  With --denoise each view written is the
+// à-trous filter of its accumulation; the unfiltered accumulation is what the
+// next view reprojects.
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
@@ -305,9 +314,14 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
 // rt_context_render_cameras_async on device 0, RT_MAX_FRAMES at a time; each
 // launch's images go to save(first frame, frames, their RGBA8 images, w*h*4
 // bytes each), which returns false to stop (RT_E_IO); fills stats.
+// tp (--temporal): view f takes seed st.seed + f; after each
+// launch its views, in order, get their feature buffers and are accumulated
+// over the view before (rt_temporal_async; features, colour and count
+// ping-pong), and the accumulated images are the ones saved -- filtered by
+// rt_denoise_async first when dn is given.
 template <class Save>
 static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int n, double degrees,
-                        Save save, rt_stats* stats) {
+                        Save save, rt_stats* stats, const rt_temporal* tp = nullptr, const rt_denoise* dn = nullptr) {
   std::vector<rt_camera> cams((size_t)n);
   int rc = rt_camera_orbit(&scene->camera, n, degrees, cams.data());
   if (rc != RT_OK) return rc;
@@ -331,6 +345,16 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
   uint8_t* d_img = nullptr;
   if (rc == RT_OK && hip_ok(hipMalloc((void**)&d_lin, (size_t)per * npix * 12), "hipMalloc"))
     hip_ok(hipMalloc((void**)&d_img, (size_t)per * npix * 4), "hipMalloc");
+  // --temporal: two sets of albedo | normal | depth | object | accumulated colour | count, and the filter's workspace
+  const size_t set_floats = npix * 12;
+  float* d_tp = nullptr;
+  void* d_work = nullptr;
+  const size_t work_bytes = dn ? rt_denoise_workspace_bytes(w, h) : 0;
+  if (rc == RT_OK && tp && hip_ok(hipMalloc((void**)&d_tp, 2 * set_floats * sizeof(float)), "hipMalloc") && dn)
+    hip_ok(hipMalloc(&d_work, work_bytes), "hipMalloc");
+  std::vector<uint64_t> seeds((size_t)n);
+  for (int f = 0; f < n; ++f) seeds[(size_t)f] = st.seed + (uint64_t)f;
+  rt_temporal_frame prev_frame = {};
   double kernel_s = 0, save_s = 0;
   for (int f0 = 0; rc == RT_OK && f0 < n; f0 += per) {
     const int m = std::min(per, n - f0);
@@ -340,19 +364,41 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
       lin[f] = d_lin + (size_t)f * npix * 3;
       img[f] = d_img + (size_t)f * npix * 4;
     }
-    rc = rt_context_render_cameras_async(ctx, w, h, &st, m, cams.data() + f0, nullptr, 0, 1, RT_LAYOUT_IMAGE, lin, img,
-                                         nullptr);
+    rc = rt_context_render_cameras_async(ctx, w, h, &st, m, cams.data() + f0, tp ? seeds.data() + f0 : nullptr, 0, 1,
+                                         RT_LAYOUT_IMAGE, lin, img, nullptr);
+    if (rc != RT_OK) break;
+    double ks = 0;  // (the render's own device time: read before the feature passes record theirs)
+    if (tp && rt_context_last_kernel_seconds(ctx, &ks) == RT_OK) kernel_s += ks;
+    for (int f = 0; tp && rc == RT_OK && f < m; ++f) {
+      float* set = d_tp + (size_t)((f0 + f) & 1) * set_floats;
+      float *albedo = set, *normal = set + npix * 3, *depth = set + npix * 6, *acc = set + npix * 8,
+            *cnt = set + npix * 11;
+      int32_t* object = (int32_t*)(set + npix * 7);
+      rt_settings fst = st;
+      fst.seed = seeds[(size_t)(f0 + f)];
+      const rt_aov_buffers out = {albedo, normal, depth, nullptr, object};
+      rc = rt_context_render_aov_async(ctx, w, h, &fst, &cams[(size_t)(f0 + f)], &out, nullptr);
+      rt_temporal_frame cur = {lin[f], depth, object, normal, nullptr, {0}};
+      if (rc == RT_OK) rc = rt_camera_frame(&cams[(size_t)(f0 + f)], st.camera, w, h, cur.frame);
+      if (rc == RT_OK) rc = rt_temporal_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, acc, cnt, img[f], nullptr);
+      prev_frame = cur;
+      prev_frame.color = acc;
+      prev_frame.count = cnt;
+      if (rc == RT_OK && dn) {
+        const rt_denoise_inputs in = {acc, normal, depth, albedo, object};
+        rc = rt_denoise_async(dn, w, h, &in, nullptr, img[f], d_work, work_bytes, nullptr);
+      }
+    }
     if (rc != RT_OK) break;
     if (!hip_ok(hipMemcpy(rgba.data(), d_img, (size_t)m * npix * 4, hipMemcpyDeviceToHost), "hipMemcpy")) break;
-    double ks = 0;
-    if (rt_context_last_kernel_seconds(ctx, &ks) == RT_OK) kernel_s += ks;
+    if (!tp && rt_context_last_kernel_seconds(ctx, &ks) == RT_OK) kernel_s += ks;
     const auto t_save = std::chrono::steady_clock::now();  // (writing the files is not render time)
     if (!save(f0, m, rgba.data())) rc = RT_E_IO;
     save_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_save).count();
   }
   const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - save_s;
-  for (void* p : {(void*)d_lin, (void*)d_img})
+  for (void* p : {(void*)d_lin, (void*)d_img, (void*)d_tp, d_work})
     if (p) (void)hipFree(p);
   rt_context_destroy(ctx);
   if (rc != RT_OK) {
@@ -527,8 +573,34 @@ static bool parse_denoise(const std::string& x, rt_denoise* dn) {
   }
 }
 
+// --temporal SPEC: `default`, or MAX_HISTORY[,DEPTH_TOL[,NORMAL_MIN]] over the defaults within
+// rt_temporal's ranges (include/rt_api.h), checked before anything is rendered
+static bool parse_temporal(const std::string& x, rt_temporal* tp) {
+  rt_temporal_default(tp);
+  if (x == "default") return true;
+  if (x.empty()) return false;
+  size_t pos = 0;
+  for (int nf = 0;; ++nf) {
+    if (nf == 3) return false;  // a fourth field
+    const size_t c = x.find(',', pos);
+    const std::string part = x.substr(pos, c == std::string::npos ? std::string::npos : c - pos);
+    char* end = nullptr;
+    errno = 0;
+    const double f = strtod(part.c_str(), &end);
+    if (part.empty() || !end || *end || errno != 0) return false;
+    (nf == 0 ? tp->max_history : nf == 1 ? tp->depth_tol : tp->normal_min) = f;
+    if (c == std::string::npos) break;
+    pos = c + 1;
+  }
+  return std::isfinite(tp->max_history) && tp->max_history >= 1 && std::isfinite(tp->depth_tol) && tp->depth_tol >= 0 &&
+         tp->normal_min >= -1 && tp->normal_min <= 1;
+}
+
 int main(int argc, char** argv) {
   std::vector<std::string> args;
+  bool temporal_on = false;    // --temporal SPEC
+  rt_temporal tpar;
+  rt_temporal_default(&tpar);
   bool denoise_on = false;     // --denoise SPEC
   rt_denoise dn;
   rt_denoise_default(&dn);
@@ -655,6 +727,14 @@ int main(int argc, char** argv) {
         return 2;
       }
       denoise_on = true;
+    } else if (a == "--temporal") {  // --orbit: write the accumulated views
+      const std::string x = need("--temporal");
+      if (!parse_temporal(x, &tpar)) {
+        fprintf(stderr, "invalid --temporal %s (default, or MAX_HISTORY[,DEPTH_TOL[,NORMAL_MIN]]: >= 1, >= 0, "
+                        "-1..1)\n", x.c_str());
+        return 2;
+      }
+      temporal_on = true;
     } else if (a == "--sky") {  // opt-in sky on miss (atmosphere.go presets); default: black
       const std::string k = need("--sky");
       if (k == "none") st.sky = RT_SKY_NONE;
@@ -686,8 +766,12 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--aov needs --samples >= 1 and one view (not with --orbit)\n");
     return 2;
   }
-  if (denoise_on && (orbit_n > 0 || st.samples < 1)) {
-    fprintf(stderr, "--denoise needs --samples >= 1 and one view (not with --orbit)\n");
+  if (temporal_on && (orbit_n <= 0 || st.samples < 1)) {
+    fprintf(stderr, "--temporal accumulates the views of --orbit and needs --samples >= 1\n");
+    return 2;
+  }
+  if (denoise_on && ((orbit_n > 0 && !temporal_on) || st.samples < 1)) {
+    fprintf(stderr, "--denoise needs --samples >= 1 and one view (with --orbit only together with --temporal)\n");
     return 2;
   }
   if (pass_samples > 0 && st.num_devices > 1) {
@@ -820,7 +904,8 @@ int main(int argc, char** argv) {
       return true;
     };
     if (rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK ||
-        render_orbit(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)orbit_n, orbit_deg, save, &stats) != RT_OK) {
+        render_orbit(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)orbit_n, orbit_deg, save, &stats,
+                     temporal_on ? &tpar : nullptr, denoise_on ? &dn : nullptr) != RT_OK) {
       if (!save_failed) fprintf(stderr, "render failed: %s\n", rt_last_error());
       rt_scene_free(sb);
       return save_failed ? 1 : 2;

@@ -1,6 +1,7 @@
 // rt_internal.h — host-side interfaces between the C ABI (rt_api.cpp and the
 // files around rt_context.h), the kernels (rt_kernel.hip, rt_stream.hip,
-// rt_image_ops.hip, rt_wavefront.hip, rt_schedule.hip, rt_adaptive.hip, rt_aov.hip, rt_denoise.hip), the
+// rt_image_ops.hip, rt_wavefront.hip, rt_schedule.hip, rt_adaptive.hip, rt_aov.hip, rt_denoise.hip,
+// rt_temporal.hip), the
 // scene loader (scene_json.cpp), the BVH builder (bvh.cpp) and the output
 // writers (image_io.cpp).
 #pragma once
@@ -12,6 +13,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/rt_api.h"
+#include "../../include/rt_temporal.h"
 #include "rt_scene_dev.h"
 
 namespace rtgo {
@@ -611,6 +613,19 @@ struct DenoiseParams {
 };
 int launch_denoise(const DenoiseParams& p, void* stream);
 int preload_denoise_kernels();
+
+// ---- temporal accumulation (rt_temporal.hip; rt_temporal_async)
+// Checked arguments of one call: the per-call constants (include/rt_temporal.h),
+// both frames' buffers and the outputs, image layout, device pointers.
+struct TemporalParams {
+  rt_tp_constants c;           // rt_tp_constants_of: parameters, both cameras, W and H
+  rt_tp_buffers cur, prev;     // prev is read only when c.has_prev
+  float* out_color;            // W*H*3, not prev.color
+  float* out_count;            // W*H, not prev.count
+  uint8_t* out_rgba;           // W*H*4, or null
+};
+int launch_temporal(const TemporalParams& p, void* stream);
+int preload_temporal_kernels();
 
 // ---------------------------------------------------------------- wavefront path
 // (rt_wavefront.hip: BVH scenes)

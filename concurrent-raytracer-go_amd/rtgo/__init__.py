@@ -250,6 +250,31 @@ class DenoiseInputs(ctypes.Structure):
     ]
 
 
+class Temporal(ctypes.Structure):
+    """rt_temporal: the parameters of temporal accumulation (default_temporal())."""
+
+    _fields_ = [
+        ("max_history", ctypes.c_double),
+        ("depth_tol", ctypes.c_double),
+        ("normal_min", ctypes.c_double),
+        ("min_weight", ctypes.c_double),
+    ]
+
+
+class TemporalFrame(ctypes.Structure):
+    """rt_temporal_frame: one frame's buffers (color and depth required; object and normal may be None / 0;
+    count is read in the previous frame only) and the 12 doubles of rt_camera_frame for its camera."""
+
+    _fields_ = [
+        ("color", ctypes.c_void_p),
+        ("depth", ctypes.c_void_p),
+        ("object", ctypes.c_void_p),
+        ("normal", ctypes.c_void_p),
+        ("count", ctypes.c_void_p),
+        ("frame", ctypes.c_double * 12),
+    ]
+
+
 class Counts(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in COUNT_FIELDS] + [("culled", ctypes.c_uint64 * 9),
                                                                ("soft_occlusion", ctypes.c_uint64 * 9),
@@ -365,6 +390,9 @@ EXPORTED_SYMBOLS = [
     "rt_denoise_workspace_bytes",
     "rt_denoise_async",
     "rt_denoise_host",
+    "rt_temporal_default",
+    "rt_temporal_async",
+    "rt_temporal_host",
 ]
 
 _lib = None
@@ -496,6 +524,11 @@ def lib():
         "rt_denoise_async": (ctypes.c_int, [ctypes.POINTER(Denoise), i32, i32, ctypes.POINTER(DenoiseInputs), vp, vp,
                                              vp, sz, vp]),
         "rt_denoise_host": (ctypes.c_int, [ctypes.POINTER(Denoise), i32, i32, ctypes.POINTER(DenoiseInputs), vp, vp]),
+        "rt_temporal_default": (None, [ctypes.POINTER(Temporal)]),
+        "rt_temporal_async": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
+                                              ctypes.POINTER(TemporalFrame), vp, vp, vp, vp]),
+        "rt_temporal_host": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
+                                             ctypes.POINTER(TemporalFrame), vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -648,6 +681,8 @@ class ParallelRenderer:
         self.last_sample_counts = None  # per-pixel samples of the last render_progressive (H x W)
         self.last_progressive_state = None  # Context.progressive_state() at its end
         self.last_denoised_linear = None  # the filter's linear output of the last denoised render (H x W x 3)
+        self.last_temporal_linear = None  # render_sequence(temporal=...): the accumulated frames (n x H x W x 3)
+        self.last_history = None  # ... and each pixel's history length (n x H x W)
 
     def set_tuning(self, tuning: Tuning):
         self._tuning = tuning
@@ -892,13 +927,34 @@ class ParallelRenderer:
         }
         return img
 
-    def render_sequence(self, scene: Scene, width: int, height: int, cameras, seeds=None) -> np.ndarray:
+    def render_sequence(self, scene: Scene, width: int, height: int, cameras, seeds=None, temporal=None,
+                        denoise=None) -> np.ndarray:
         """The scene from each of ``cameras`` (Camera structs or scene-file camera dicts; any number):
         an (n, H, W, 4) uint8 array, frame f that of ``render`` with the scene's camera replaced by
         cameras[f] and seed seeds[f] (None: the renderer's seed), byte for byte.
         On one device, with a context of its own, in launches of at most RT_MAX_FRAMES frames
-        (Context.render_cameras_async).  ``last_linear`` becomes (n, H, W, 3) float32."""
+        (Context.render_cameras_async).  ``last_linear`` becomes (n, H, W, 3) float32.
+
+        temporal (True, a dict of Temporal's fields or a Temporal): the frames render as
+        above, each gets a feature pass with its own camera, seed and samples, and they are accumulated in
+        order on the device (rt_temporal_async: frame f's history is frame f - 1's result; the feature
+        buffers ping-pong).  The returned frames are the ACCUMULATED ones; ``last_linear`` stays the raw
+        renders, ``last_temporal_linear`` is (n, H, W, 3) float32 and ``last_history`` (n, H, W) float32
+        (each pixel's history length).  With seeds None, frame f then takes seed settings.seed + f: the same
+        seed for every frame would repeat the same screen-locked noise, which accumulation cannot remove.
+
+        denoise (True, a dict or a Denoise; §4.13; only together with ``temporal``, as the CLI's --denoise
+        with --orbit): frame f's returned image is rt_denoise_async of its accumulated colour with its own
+        features; what is fed back to the next frame is the unfiltered accumulation.
+        ``last_denoised_linear`` is (n, H, W, 3).  A call without ``temporal`` / ``denoise`` sets the
+        attributes of what it did not compute to None."""
         t0 = time.perf_counter()
+        tp = None if temporal is None or temporal is False else _as_temporal(temporal)
+        dn = None if denoise is None or denoise is False else _as_denoise(denoise)
+        if dn is not None and tp is None:
+            raise RenderError("render_sequence: denoise filters the accumulated frames and needs temporal")
+        if tp is not None and int(self.settings.samples) < 1:
+            raise RenderError("render_sequence: temporal needs settings.samples >= 1")
         if (len(self.devices) if self.devices else max(1, self.settings.num_devices)) > 1:
             raise RenderError("render_sequence renders on one device (sequences over several GPUs are not supported)")
         cams = [_as_camera(c) for c in cameras]
@@ -907,6 +963,8 @@ class ParallelRenderer:
             raise RenderError("render_sequence: at least one camera is needed")
         if seeds is not None and len(seeds) != n:
             raise RenderError(f"render_sequence: {len(seeds)} seeds for {n} cameras")
+        if seeds is None and tp is not None:
+            seeds = [(int(self.settings.seed) + f) & (2 ** 64 - 1) for f in range(n)]
         _check(lib().rt_validate(ctypes.byref(scene.view), width, height, ctypes.byref(self.settings)))
         import torch
 
@@ -927,8 +985,43 @@ class ParallelRenderer:
                                          [lin[f].data_ptr() for f in range(f0, f1)],
                                          [rgba[f].data_ptr() for f in range(f0, f1)],
                                          seeds=None if seeds is None else [int(s) for s in seeds[f0:f1]], stream=0)
+            if tp is not None:
+                # per frame: its features, the accumulation into its own slot (frame f - 1's slot is the
+                # history, so no output is ever the buffer the taps read), the filter over the result
+                feat = [{k: torch.zeros(npix * (3 if k in ("albedo", "normal") else 1),
+                                        dtype=torch.int32 if k == "object" else torch.float32, device="cuda")
+                         for k in ("albedo", "normal", "depth", "object")} for _ in range(2)]
+                acc = torch.zeros((n, npix * 3), dtype=torch.float32, device="cuda")
+                cnt = torch.zeros((n, npix), dtype=torch.float32, device="cuda")
+                if dn is not None:
+                    nbytes = denoise_workspace_bytes(width, height)
+                    work = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+                    dlin = torch.zeros((n, npix * 3), dtype=torch.float32, device="cuda")
+                fst = Settings.from_buffer_copy(self.settings)
+                prev = None
+                for f in range(n):
+                    ft = feat[f & 1]
+                    fst.seed = int(seeds[f]) & (2 ** 64 - 1)
+                    ctx.render_aov_async(width, height, fst,
+                                         AovBuffers(ft["albedo"].data_ptr(), ft["normal"].data_ptr(),
+                                                    ft["depth"].data_ptr(), None, ft["object"].data_ptr()),
+                                         camera=cams[f], stream=0)
+                    cur = temporal_frame(camera_frame(cams[f], int(self.settings.camera), width, height),
+                                         lin[f].data_ptr(), ft["depth"].data_ptr(), ft["object"].data_ptr(),
+                                         ft["normal"].data_ptr())
+                    temporal_async(width, height, cur, prev, acc[f].data_ptr(), cnt[f].data_ptr(),
+                                   rgba[f].data_ptr(), tp, 0)
+                    prev = temporal_frame(cur.frame, acc[f].data_ptr(), ft["depth"].data_ptr(),
+                                          ft["object"].data_ptr(), ft["normal"].data_ptr(), cnt[f].data_ptr())
+                    if dn is not None:
+                        denoise_async(width, height, acc[f].data_ptr(), ft["normal"].data_ptr(), ft["depth"].data_ptr(),
+                                      ft["albedo"].data_ptr(), ft["object"].data_ptr(), dlin[f].data_ptr(),
+                                      rgba[f].data_ptr(), work.data_ptr(), nbytes, dn, 0)
             torch.cuda.synchronize()
             self.last_linear = lin.cpu().numpy().reshape(n, height, width, 3)
+            self.last_temporal_linear = acc.cpu().numpy().reshape(n, height, width, 3) if tp is not None else None
+            self.last_history = cnt.cpu().numpy().reshape(n, height, width) if tp is not None else None
+            self.last_denoised_linear = dlin.cpu().numpy().reshape(n, height, width, 3) if dn is not None else None
             img = rgba.cpu().numpy().reshape(n, height, width, 4)
         self.benchmark_data = {
             "scene_name": "demo_scene",
@@ -1422,6 +1515,86 @@ def denoise_host(color, normal, depth, albedo=None, object=None, params=None):
     rgba = np.zeros((h, w, 4), np.uint8)
     _check(lib().rt_denoise_host(ctypes.byref(p), w, h, ctypes.byref(inp), lin.ctypes.data, rgba.ctypes.data))
     return lin, rgba
+
+
+def default_temporal(**over) -> Temporal:
+    """rt_temporal_default (max_history 32, depth_tol 0.05, normal_min 0.9, min_weight 0.25), with the
+    given fields replaced."""
+    t = Temporal()
+    lib().rt_temporal_default(ctypes.byref(t))
+    for k, v in over.items():
+        if k not in ("max_history", "depth_tol", "normal_min", "min_weight"):
+            raise RenderError(f"default_temporal: no such field {k}")
+        setattr(t, k, v)
+    return t
+
+
+def _as_temporal(params) -> Temporal:
+    """None or True: the defaults; a Temporal as it is; a dict: default_temporal(**dict)."""
+    if params is None or params is True:
+        return default_temporal()
+    if isinstance(params, Temporal):
+        return params
+    if isinstance(params, dict):
+        return default_temporal(**params)
+    raise RenderError("temporal parameters are a Temporal, a dict of its fields, True or None")
+
+
+def temporal_frame(frame, color, depth, object=None, normal=None, count=None) -> TemporalFrame:
+    """An rt_temporal_frame from pointers (ints; None: not given) and the 12 doubles of camera_frame."""
+    f = np.ascontiguousarray(frame, np.float64).ravel()
+    if f.size != 12:
+        raise RenderError("temporal: a frame is the 12 doubles of camera_frame")
+    return TemporalFrame(color, depth, object, normal, count, (ctypes.c_double * 12)(*[float(v) for v in f]))
+
+
+def temporal_async(width: int, height: int, cur: TemporalFrame, prev, d_out_color: int, d_out_count: int,
+                   d_out_rgba=None, params=None, stream: int = 0):
+    """rt_temporal_async: cur and prev (None: start a history) are TemporalFrames of
+    device pointers (temporal_frame()); the outputs are device pointers, d_out_rgba may be None;
+    asynchronous on ``stream``.  d_out_color / d_out_count must not be prev's color / count."""
+    p = _as_temporal(params)
+    _check(lib().rt_temporal_async(ctypes.byref(p), width, height, ctypes.byref(cur),
+                                   ctypes.byref(prev) if prev is not None else None, ctypes.c_void_p(d_out_color),
+                                   ctypes.c_void_p(d_out_count), ctypes.c_void_p(d_out_rgba), ctypes.c_void_p(stream)))
+
+
+def temporal_host(cur: dict, prev=None, params=None):
+    """rt_temporal_host: temporal accumulation on numpy arrays, without a device.  cur and prev (None:
+    start a history) are dicts with ``color`` (H, W, 3) float32, ``depth`` (H, W) float32, ``frame`` (the
+    12 doubles of camera_frame), optionally ``object`` (H, W) int32 and ``normal`` (H, W, 3) float32 (each
+    in both frames or in neither), and in prev ``count`` (H, W) float32 -- the previous call's results.
+    Returns (color (H, W, 3) float32, count (H, W) float32, rgba (H, W, 4) uint8)."""
+    color = np.ascontiguousarray(cur["color"], np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise RenderError("temporal_host: color is an (H, W, 3) array")
+    h, w = color.shape[:2]
+    keep = []
+
+    def frame_of(d, name):
+        def arr(k, dtype, shape):
+            a = d.get(k)
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype)
+            if a.shape != shape:
+                raise RenderError(f"temporal_host: {name}.{k} has shape {a.shape}, expected {shape}")
+            keep.append(a)
+            return a.ctypes.data
+
+        return temporal_frame(d["frame"], arr("color", np.float32, (h, w, 3)), arr("depth", np.float32, (h, w)),
+                              arr("object", np.int32, (h, w)), arr("normal", np.float32, (h, w, 3)),
+                              arr("count", np.float32, (h, w)))
+
+    fc = frame_of(cur, "cur")
+    fp = frame_of(prev, "prev") if prev is not None else None
+    p = _as_temporal(params)
+    out = np.zeros((h, w, 3), np.float32)
+    cnt = np.zeros((h, w), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    _check(lib().rt_temporal_host(ctypes.byref(p), w, h, ctypes.byref(fc), ctypes.byref(fp) if fp is not None else None,
+                                  out.ctypes.data, cnt.ctypes.data, rgba.ctypes.data))
+    return out, cnt, rgba
 
 
 def max_local_tiles(width: int, height: int, world: int) -> int:

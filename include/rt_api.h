@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async, rt_denoise, rt_denoise_inputs, rt_denoise_default, rt_denoise_workspace_bytes, rt_denoise_async, rt_denoise_host); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async, rt_denoise, rt_denoise_inputs, rt_denoise_default, rt_denoise_workspace_bytes, rt_denoise_async, rt_denoise_host, rt_temporal, rt_temporal_frame, rt_temporal_default, rt_temporal_async, rt_temporal_host); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -741,6 +741,117 @@ int rt_denoise_async(const rt_denoise* params, int32_t width, int32_t height, co
                      void* hip_stream);
 int rt_denoise_host(const rt_denoise* params, int32_t width, int32_t height, const rt_denoise_inputs* in,
                     float* out_linear, uint8_t* out_rgba);
+
+/* Temporal accumulation over a camera sequence: the previous
+ * frame's accumulated colour is reprojected into the current frame through the
+ * current frame's depth and the two cameras, and blended with the current
+ * render, so that a moving preview of a static scene gathers samples from
+ * frame to frame instead of starting from none.  It traces no ray.  The
+ * project's own feature, defined here to the bit like rt_denoise_async:
+ * binary64 `+ - * /`, comparisons and floor only, in one written order, floats
+ * widened before use and rounded once on store, so that the device kernel,
+ * rt_temporal_host and a restatement in any language agree exactly
+ * (include/rt_temporal.h is the code both sides run).
+ *
+ * A frame (rt_temporal_frame), laid out as rt_context_render_async and
+ * rt_aov_buffers lay their buffers out (pixel (x, y) at y * W + x, row 0 the
+ * bottom):
+ *   color   float3  required: cur = this frame's render (d_linear); prev = the
+ *                   PREVIOUS CALL's out_color
+ *   depth   float   required: rt_aov_buffers.d_depth of that frame
+ *   object  int32   optional (NULL: no id test)
+ *   normal  float3  optional (NULL: no normal test)
+ *   count   float   prev only: the previous call's out_count; ignored in cur
+ *   frame   12 doubles: rt_camera_frame of that frame's camera -- origin o,
+ *                   lower_left l, horizontal h, vertical v_vec
+ * object and normal must each be NULL in both frames or in neither.
+ * valid(p) means cur.depth[p] is finite (a miss has +Inf).
+ *
+ * Parameters (rt_temporal; rt_temporal_default sets the defaults):
+ *   max_history  >= 1, finite                          default 32
+ *   depth_tol    >= 0, finite; 0: no depth test        default 0.05
+ *   normal_min   in [-1, 1]; -1 stops no unit normals  default 0.9
+ *   min_weight   in (0, 1]                             default 0.25
+ * Anything else, NaN included, is RT_E_INVALID.
+ *
+ * Per call, on the host, with o', l', h', v' the previous frame's vectors and
+ * dot(a, b) = (a0 * b0 + a1 * b1) + a2 * b2:
+ *   g = l' - o'                       per component
+ *   a = (g + h' * 0.5) + v' * 0.5     the previous camera's centre ray: its view axis
+ *   aa = dot(a, a), hh = dot(h', h'), vv = dot(v', v')
+ * RT_E_INVALID when any of the 24 frame doubles is not finite or when aa, hh
+ * or vv is not > 0.
+ *
+ * Per pixel p = (x, y):
+ *   1. p is not valid: out_color = cur.color bit for bit, out_count = 0.
+ *   2. prev == NULL: out_color = cur.color bit for bit, out_count = 1.
+ *   3. The world point.  u = (x + 0.5) / W, v = (y + 0.5) / H,
+ *      dir = ((l + h * u) + v_vec * v) - o, P = o + dir * z with z = cur.depth[p],
+ *      d = P - o', all per component.  `depth` is T with the view-axis component
+ *      of the direction exactly 1 (see rt_aov_buffers), so no root is taken.
+ *   4. Into the previous camera.  t = dot(d, a) / aa; no history unless t > 0.
+ *      e = d / t - g per component; fx = (dot(e, h') / hh) * W - 0.5 and
+ *      fy = (dot(e, v') / vv) * H - 0.5; no history unless
+ *      fx > -1 && fx < W && fy > -1 && fy < H (comparisons a NaN fails).
+ *   5. The bilinear fetch.  ix = (int)floor(fx), wx = fx - floor(fx), likewise
+ *      iy and wy.  sumw, sum[3] and sumn start at 0; the taps in this order:
+ *      j = 0, 1 in the outer loop, i = 0, 1 in the inner loop, q = (ix + i, iy + j).
+ *      A tap is skipped when q is outside the image; when prev.depth[q] is not
+ *      finite; when ids are given and prev.object[q] != cur.object[p]; when
+ *      normals are given and dot(cur.normal[p], prev.normal[q]) < normal_min;
+ *      when depth_tol > 0 and |prev.depth[q] - t| > depth_tol * t (|r| is
+ *      r < 0 ? -r : r).  Otherwise w = (i ? wx : 1 - wx) * (j ? wy : 1 - wy),
+ *      sumw += w, sum[k] += w * prev.color[q][k], sumn += w * prev.count[q].
+ *      There is a history iff sumw >= min_weight.
+ *   6. The blend.  hist[k] = sum[k] / sumw, n = sumn / sumw, n1 = n + 1, and
+ *      n1 = max_history when n1 > max_history;
+ *      out_color[k] = (float)(hist[k] + ((double)cur.color[k] - hist[k]) / n1),
+ *      out_count = (float)n1.  With no history: out_color = cur.color bit for
+ *      bit, out_count = 1.
+ *   7. out_rgba, if given, is rt_tonemap_rgba of the stored out_color.
+ * A pixel that keeps its history is the running mean of its frames until
+ * max_history, then an exponential average with weight 1 / max_history.
+ *
+ * Every address comes from x, y and the guarded integers ix, iy: non-finite
+ * colours, depth <= 0 and absurd cameras cannot fault; their values carry no
+ * contract.  Taps read neighbours, so out_color / out_count must not be
+ * prev.color / prev.count -- the caller ping-pongs two pairs of buffers; equal
+ * pointers are refused, any other overlap carries no contract.
+ *
+ * What it can and cannot do.  `depth` is the MEAN T of a pixel's jittered
+ * samples, so P is the pixel centre's surface point only to within the pixel's
+ * footprint: at a silhouette or a sharp edge the mean mixes surfaces, and the
+ * depth, id and normal tests are what reject such taps.  The scene is static,
+ * so direct light and shadows reproject correctly.  What a mirror SHOWS does
+ * not: a reflection moves differently from the surface that carries it, so
+ * reflections on metal lag and smear while the camera moves (DESIGN.md §4.14
+ * has the figures).  max_history is the control for that: it bounds how long
+ * an old frame keeps its weight.
+ *
+ * rt_temporal_async needs no workspace and no context and allocates nothing.
+ * Every buffer pointer is a DEVICE pointer of the current device; the structs
+ * are read before the call returns; the call is asynchronous on `hip_stream`.
+ * d_out_rgba may be NULL.  RT_E_INVALID with a message, nothing enqueued and
+ * no buffer touched: NULL params or cur; a NULL color or depth; a NULL
+ * prev.count; object or normal given in one frame only; NULL d_out_color or
+ * d_out_count; d_out_color == prev.color or d_out_count == prev.count; a size
+ * that rt_validate refuses; parameters out of range; the frame rules above.
+ * rt_temporal_host does the same with host pointers and no device. */
+typedef struct { double max_history; double depth_tol; double normal_min; double min_weight; } rt_temporal;
+typedef struct {
+  const float* color;     /* W*H*3, required */
+  const float* depth;     /* W*H,   required */
+  const int32_t* object;  /* W*H   or NULL */
+  const float* normal;    /* W*H*3 or NULL */
+  const float* count;     /* W*H,   prev only */
+  double frame[12];       /* rt_camera_frame: origin, lower_left, horizontal, vertical */
+} rt_temporal_frame;
+void rt_temporal_default(rt_temporal* t);
+int rt_temporal_async(const rt_temporal* params, int32_t width, int32_t height, const rt_temporal_frame* cur,
+                      const rt_temporal_frame* prev /* NULL: start a history */, float* d_out_color,
+                      float* d_out_count, uint8_t* d_out_rgba /* may be NULL */, void* hip_stream);
+int rt_temporal_host(const rt_temporal* params, int32_t width, int32_t height, const rt_temporal_frame* cur,
+                     const rt_temporal_frame* prev, float* out_color, float* out_count, uint8_t* out_rgba);
 
 /* What a context has done so far (diagnostics): work schedules built (a new
  * scene, frame, rank or settings key; a measured re-cut counts too),
