@@ -9,6 +9,7 @@
 //             [--orbit N[,DEGREES]] [--aov PREFIX]
 //             [--denoise default|LEVELS[,SIGMA_COLOR[,SIGMA_DEPTH[,NORMAL_POWER]]]]
 //             [--temporal default|MAX_HISTORY[,DEPTH_TOL[,NORMAL_MIN]]]
+//             [--denoise-variance default|LEVELS[,SIGMA_LUM[,SIGMA_DEPTH[,NORMAL_POWER]]]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -65,6 +66,17 @@
 // replace the defaults from the left.  With --denoise each view written is the
 // à-trous filter of its accumulation; the unfiltered accumulation is what the
 // next view reprojects.
+// --denoise-variance SPEC (--samples >= 1, a size with pixels;
+// not with --denoise or --pass-samples) writes the variance-guided filter's
+// image.  With --orbit N --temporal ... each view's accumulation also carries
+// the luminance moments (rt_temporal_moments_async), rt_variance_async turns
+// them into the view's variance and rt_denoise_var_async filters the
+// accumulation; the unfiltered accumulation and moments are what the next view
+// reprojects.  Without --orbit the single render is filtered with the spatial
+// variance estimate (a single frame has no moments).  SPEC is `default`
+// (rt_denoise_var_default, rt_variance_default) or up to four comma-separated
+// fields that replace the defaults from the left; SIGMA_DEPTH and NORMAL_POWER
+// go to the variance pass too.
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
@@ -318,10 +330,17 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
 // launch its views, in order, get their feature buffers and are accumulated
 // over the view before (rt_temporal_async; features, colour and count
 // ping-pong), and the accumulated images are the ones saved -- filtered by
-// rt_denoise_async first when dn is given.
+// rt_denoise_async first when dn is given.  vs (--denoise-variance, §4.15): the
+// accumulation is rt_temporal_moments_async's, the moments ping-pong with it,
+// and the image saved is rt_denoise_var_async's, steered by rt_variance_async.
+struct VarianceSpec {
+  rt_denoise_var dv;
+  rt_variance vr;
+};
 template <class Save>
 static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int n, double degrees,
-                        Save save, rt_stats* stats, const rt_temporal* tp = nullptr, const rt_denoise* dn = nullptr) {
+                        Save save, rt_stats* stats, const rt_temporal* tp = nullptr, const rt_denoise* dn = nullptr,
+                        const VarianceSpec* vs = nullptr) {
   std::vector<rt_camera> cams((size_t)n);
   int rc = rt_camera_orbit(&scene->camera, n, degrees, cams.data());
   if (rc != RT_OK) return rc;
@@ -345,13 +364,15 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
   uint8_t* d_img = nullptr;
   if (rc == RT_OK && hip_ok(hipMalloc((void**)&d_lin, (size_t)per * npix * 12), "hipMalloc"))
     hip_ok(hipMalloc((void**)&d_img, (size_t)per * npix * 4), "hipMalloc");
-  // --temporal: two sets of albedo | normal | depth | object | accumulated colour | count, and the filter's workspace
-  const size_t set_floats = npix * 12;
+  // --temporal: two sets of albedo | normal | depth | object | accumulated colour | count (| moments | variance
+  // with --denoise-variance), and the filter's workspace
+  const size_t set_floats = npix * (vs ? 15 : 12);
   float* d_tp = nullptr;
   void* d_work = nullptr;
-  const size_t work_bytes = dn ? rt_denoise_workspace_bytes(w, h) : 0;
-  if (rc == RT_OK && tp && hip_ok(hipMalloc((void**)&d_tp, 2 * set_floats * sizeof(float)), "hipMalloc") && dn)
+  const size_t work_bytes = dn ? rt_denoise_workspace_bytes(w, h) : vs ? rt_denoise_var_workspace_bytes(w, h) : 0;
+  if (rc == RT_OK && tp && hip_ok(hipMalloc((void**)&d_tp, 2 * set_floats * sizeof(float)), "hipMalloc") && (dn || vs))
     hip_ok(hipMalloc(&d_work, work_bytes), "hipMalloc");
+  const float* prev_moments = nullptr;
   std::vector<uint64_t> seeds((size_t)n);
   for (int f = 0; f < n; ++f) seeds[(size_t)f] = st.seed + (uint64_t)f;
   rt_temporal_frame prev_frame = {};
@@ -380,7 +401,19 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
       rc = rt_context_render_aov_async(ctx, w, h, &fst, &cams[(size_t)(f0 + f)], &out, nullptr);
       rt_temporal_frame cur = {lin[f], depth, object, normal, nullptr, {0}};
       if (rc == RT_OK) rc = rt_camera_frame(&cams[(size_t)(f0 + f)], st.camera, w, h, cur.frame);
-      if (rc == RT_OK) rc = rt_temporal_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, acc, cnt, img[f], nullptr);
+      float *mom = set + npix * 12, *var = set + npix * 14;  // (only with vs)
+      if (rc == RT_OK && !vs)
+        rc = rt_temporal_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, acc, cnt, img[f], nullptr);
+      if (rc == RT_OK && vs) {
+        rc = rt_temporal_moments_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, albedo, prev_moments, acc, cnt,
+                                       mom, nullptr, nullptr);
+        prev_moments = mom;
+        const rt_variance_inputs vin = {acc, normal, depth, albedo, object, mom, cnt};
+        if (rc == RT_OK) rc = rt_variance_async(&vs->vr, w, h, &vin, var, nullptr);
+        const rt_denoise_inputs in = {acc, normal, depth, albedo, object};
+        if (rc == RT_OK)
+          rc = rt_denoise_var_async(&vs->dv, w, h, &in, var, nullptr, img[f], nullptr, d_work, work_bytes, nullptr);
+      }
       prev_frame = cur;
       prev_frame.color = acc;
       prev_frame.count = cnt;
@@ -500,26 +533,27 @@ static int write_aov(const rt_scene* scene, int32_t w, int32_t h, const rt_setti
 // frame's linear radiance `linear` (host, w*h*3) on device 0: the first-hit
 // feature buffers of the frame with feature_samples samples (st's seed and
 // camera model), then the filter; rgba (host, w*h*4) receives its tone-mapped
-// output.
+// output.  vs (--denoise-variance): the filter is
+// rt_denoise_var_async, steered by rt_variance_async's spatial estimate.
 static int denoise_image(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int feature_samples,
-                         const rt_denoise& dn, const float* linear, uint8_t* rgba) {
+                         const rt_denoise& dn, const float* linear, uint8_t* rgba, const VarianceSpec* vs = nullptr) {
   const size_t npix = (size_t)w * (size_t)h;
   rt_context* ctx = nullptr;
   int rc = rt_context_create(0, &ctx);
   if (rc != RT_OK) return rc;
   rc = rt_context_set_scene(ctx, scene, 0);
-  // one device block: color | albedo | normal | depth | object, then the image and the workspace
+  // one device block: color | albedo | normal | depth | object | variance, then the image and the workspace
   float* d = nullptr;
   uint8_t* d_rgba = nullptr;
   void* d_work = nullptr;
-  const size_t work_bytes = rt_denoise_workspace_bytes(w, h);
+  const size_t work_bytes = vs ? rt_denoise_var_workspace_bytes(w, h) : rt_denoise_workspace_bytes(w, h);
   auto hip_ok = [&](hipError_t e, const char* what) {
     if (e == hipSuccess) return true;
     fprintf(stderr, "%s failed: %s\n", what, hipGetErrorString(e));
     rc = RT_E_DEVICE;
     return false;
   };
-  if (rc == RT_OK && hip_ok(hipMalloc((void**)&d, npix * 11 * sizeof(float)), "hipMalloc") &&
+  if (rc == RT_OK && hip_ok(hipMalloc((void**)&d, npix * 12 * sizeof(float)), "hipMalloc") &&
       hip_ok(hipMalloc((void**)&d_rgba, npix * 4), "hipMalloc") && hip_ok(hipMalloc(&d_work, work_bytes), "hipMalloc"))
     hip_ok(hipMemcpy(d, linear, npix * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
   if (rc == RT_OK) {
@@ -530,7 +564,14 @@ static int denoise_image(const rt_scene* scene, int32_t w, int32_t h, const rt_s
   }
   if (rc == RT_OK) {
     const rt_denoise_inputs in = {d, d + npix * 6, d + npix * 9, d + npix * 3, (const int32_t*)(d + npix * 10)};
-    rc = rt_denoise_async(&dn, w, h, &in, nullptr, d_rgba, d_work, work_bytes, nullptr);
+    if (vs) {
+      const rt_variance_inputs vin = {in.color, in.normal, in.depth, in.albedo, in.object, nullptr, nullptr};
+      rc = rt_variance_async(&vs->vr, w, h, &vin, d + npix * 11, nullptr);
+      if (rc == RT_OK)
+        rc = rt_denoise_var_async(&vs->dv, w, h, &in, d + npix * 11, nullptr, d_rgba, nullptr, d_work, work_bytes, nullptr);
+    } else {
+      rc = rt_denoise_async(&dn, w, h, &in, nullptr, d_rgba, d_work, work_bytes, nullptr);
+    }
   }
   if (rc == RT_OK) hip_ok(hipMemcpy(rgba, d_rgba, npix * 4, hipMemcpyDeviceToHost), "hipMemcpy");
   const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
@@ -573,6 +614,27 @@ static bool parse_denoise(const std::string& x, rt_denoise* dn) {
   }
 }
 
+// --denoise-variance SPEC: `default`, or LEVELS[,SIGMA_LUM[,SIGMA_DEPTH[,NORMAL_POWER]]] over the defaults within
+// rt_denoise_var's ranges (include/rt_api.h), checked before anything is rendered; SIGMA_DEPTH and NORMAL_POWER
+// are the variance pass's too
+static bool parse_denoise_variance(const std::string& x, VarianceSpec* vs) {
+  rt_denoise_var_default(&vs->dv);
+  rt_variance_default(&vs->vr);
+  if (x == "default") return true;
+  rt_denoise dn;  // (the same four fields in the same places: sigma_color stands for SIGMA_LUM)
+  if (!parse_denoise(x, &dn)) return false;
+  const bool has2 = std::count(x.begin(), x.end(), ',') >= 1, has3 = std::count(x.begin(), x.end(), ',') >= 2,
+             has4 = std::count(x.begin(), x.end(), ',') >= 3;
+  vs->dv.levels = dn.levels;
+  if (has2) vs->dv.sigma_lum = dn.sigma_color;
+  if (has3) vs->dv.sigma_depth = vs->vr.sigma_depth = dn.sigma_depth;
+  if (has4) vs->dv.normal_power = vs->vr.normal_power = dn.normal_power;
+  const int32_t np = vs->dv.normal_power;
+  return vs->dv.levels >= 1 && vs->dv.levels <= 8 && np >= 0 && np <= 128 && (np & (np - 1)) == 0 &&
+         std::isfinite(vs->dv.sigma_lum) && vs->dv.sigma_lum >= 0 && std::isfinite(vs->dv.sigma_depth) &&
+         vs->dv.sigma_depth >= 0;
+}
+
 // --temporal SPEC: `default`, or MAX_HISTORY[,DEPTH_TOL[,NORMAL_MIN]] over the defaults within
 // rt_temporal's ranges (include/rt_api.h), checked before anything is rendered
 static bool parse_temporal(const std::string& x, rt_temporal* tp) {
@@ -604,6 +666,10 @@ int main(int argc, char** argv) {
   bool denoise_on = false;     // --denoise SPEC
   rt_denoise dn;
   rt_denoise_default(&dn);
+  bool variance_on = false;    // --denoise-variance SPEC
+  VarianceSpec vspec;
+  rt_denoise_var_default(&vspec.dv);
+  rt_variance_default(&vspec.vr);
   std::string aov_prefix;      // --aov PREFIX (empty: no feature buffers)
   long long orbit_n = 0;       // --orbit N[,DEGREES] (0: one render)
   double orbit_deg = 360.0;
@@ -727,6 +793,14 @@ int main(int argc, char** argv) {
         return 2;
       }
       denoise_on = true;
+    } else if (a == "--denoise-variance") {  // write the variance-guided filter's image
+      const std::string x = need("--denoise-variance");
+      if (!parse_denoise_variance(x, &vspec)) {
+        fprintf(stderr, "invalid --denoise-variance %s (default, or LEVELS[,SIGMA_LUM[,SIGMA_DEPTH[,NORMAL_POWER]]]: "
+                        "1..8, >= 0, >= 0, 0 or a power of two <= 128)\n", x.c_str());
+        return 2;
+      }
+      variance_on = true;
     } else if (a == "--temporal") {  // --orbit: write the accumulated views
       const std::string x = need("--temporal");
       if (!parse_temporal(x, &tpar)) {
@@ -774,6 +848,12 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--denoise needs --samples >= 1 and one view (with --orbit only together with --temporal)\n");
     return 2;
   }
+  if (variance_on && (denoise_on || pass_samples > 0 || (orbit_n > 0 && !temporal_on) || st.samples < 1)) {
+    fprintf(stderr, "--denoise-variance needs --samples >= 1 and one plain render, or --orbit together with --temporal; "
+                    "not with --denoise or --pass-samples\n");
+    return 2;
+  }
+  if (variance_on) denoise_on = true;  // (from here on: the filtered image is the one written; vspec says by which filter)
   if (pass_samples > 0 && st.num_devices > 1) {
     fprintf(stderr, "--pass-samples renders on one device (--devices %d)\n", st.num_devices);
     return 2;
@@ -811,7 +891,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (denoise_on && (w <= 0 || h <= 0)) {
-    fprintf(stderr, "--denoise needs a size with pixels (%lldx%lld)\n", w, h);
+    fprintf(stderr, "%s needs a size with pixels (%lldx%lld)\n", variance_on ? "--denoise-variance" : "--denoise", w, h);
     return 2;
   }
   printf("Loading scene from: %s\n", scene_file.c_str());
@@ -905,7 +985,8 @@ int main(int argc, char** argv) {
     };
     if (rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK ||
         render_orbit(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)orbit_n, orbit_deg, save, &stats,
-                     temporal_on ? &tpar : nullptr, denoise_on ? &dn : nullptr) != RT_OK) {
+                     temporal_on ? &tpar : nullptr, denoise_on && !variance_on ? &dn : nullptr,
+                     variance_on ? &vspec : nullptr) != RT_OK) {
       if (!save_failed) fprintf(stderr, "render failed: %s\n", rt_last_error());
       rt_scene_free(sb);
       return save_failed ? 1 : 2;
@@ -997,7 +1078,8 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (denoise_on &&
-      denoise_image(scene, (int32_t)w, (int32_t)h, st, st.samples, dn, linear.data(), rgba.data()) != RT_OK) {
+      denoise_image(scene, (int32_t)w, (int32_t)h, st, st.samples, dn, linear.data(), rgba.data(),
+                    variance_on ? &vspec : nullptr) != RT_OK) {
     fprintf(stderr, "denoise failed: %s\n", rt_last_error());
     rt_renderer_destroy(rr);
     rt_scene_free(sb);

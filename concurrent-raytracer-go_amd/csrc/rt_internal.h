@@ -1,7 +1,7 @@
 // rt_internal.h — host-side interfaces between the C ABI (rt_api.cpp and the
 // files around rt_context.h), the kernels (rt_kernel.hip, rt_stream.hip,
 // rt_image_ops.hip, rt_wavefront.hip, rt_schedule.hip, rt_adaptive.hip, rt_aov.hip, rt_denoise.hip,
-// rt_temporal.hip), the
+// rt_temporal.hip, rt_variance.hip), the
 // scene loader (scene_json.cpp), the BVH builder (bvh.cpp) and the output
 // writers (image_io.cpp).
 #pragma once
@@ -14,6 +14,7 @@
 
 #include "../../include/rt_api.h"
 #include "../../include/rt_temporal.h"
+#include "../../include/rt_variance.h"
 #include "rt_scene_dev.h"
 
 namespace rtgo {
@@ -626,6 +627,42 @@ struct TemporalParams {
 };
 int launch_temporal(const TemporalParams& p, void* stream);
 int preload_temporal_kernels();
+
+// ---- variance-guided denoising (rt_variance.hip; rt_temporal_moments_async, rt_variance_async,
+// rt_denoise_var_async).  Checked arguments of one call each, image layout, device pointers.
+struct TemporalMomentsParams {
+  TemporalParams t;            // rt_temporal_async's arguments
+  const float* cur_albedo;     // W*H*3, or null
+  const float* prev_moments;   // W*H*2, given exactly when t.c.has_prev
+  float* out_moments;          // W*H*2, not prev_moments
+};
+struct VarianceParams {
+  rt_variance vr;              // checked
+  int32_t W, H;
+  rt_vr_buffers in;            // color, normal, depth; albedo, object, moments + count or null
+  float* out_var;              // W*H
+};
+// The filter's workspace holds two colour records that ping-pong ({e[3], var}, 16 bytes each), the guide
+// record (16 bytes) and the id plane (4 bytes) per pixel, 256-byte aligned by the launcher.
+constexpr size_t kDenoiseVarRecordBytes = 52;  // per pixel
+struct DenoiseVarParams {
+  rt_denoise_var dn;           // checked
+  int32_t W, H;
+  const float* color;          // W*H*3
+  const float* normal;         // W*H*3
+  const float* depth;          // W*H
+  const float* albedo;         // W*H*3, or null: no demodulation (also when dn.demodulate is 0)
+  const int32_t* object;       // W*H, or null
+  const float* variance;       // W*H
+  float* out_linear;           // W*H*3 (may be color), or null
+  uint8_t* out_rgba;           // W*H*4, or null
+  float* out_variance;         // W*H (may be variance), or null
+  void* workspace;             // at least kDenoiseVarRecordBytes * W * H + kDenoiseAlign bytes
+};
+int launch_temporal_moments(const TemporalMomentsParams& p, void* stream);
+int launch_variance(const VarianceParams& p, void* stream);
+int launch_denoise_var(const DenoiseVarParams& p, void* stream);
+int preload_variance_kernels();
 
 // ---------------------------------------------------------------- wavefront path
 // (rt_wavefront.hip: BVH scenes)

@@ -275,6 +275,45 @@ class TemporalFrame(ctypes.Structure):
     ]
 
 
+class Variance(ctypes.Structure):
+    """rt_variance: the parameters of the variance pass (default_variance())."""
+
+    _fields_ = [
+        ("min_history", ctypes.c_double),
+        ("sigma_depth", ctypes.c_double),
+        ("normal_power", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+    ]
+
+
+class VarianceInputs(ctypes.Structure):
+    """rt_variance_inputs: color, normal and depth are required; albedo and object may be None / 0;
+    moments and count are given both or neither."""
+
+    _fields_ = [
+        ("color", ctypes.c_void_p),
+        ("normal", ctypes.c_void_p),
+        ("depth", ctypes.c_void_p),
+        ("albedo", ctypes.c_void_p),
+        ("object", ctypes.c_void_p),
+        ("moments", ctypes.c_void_p),
+        ("count", ctypes.c_void_p),
+    ]
+
+
+class DenoiseVar(ctypes.Structure):
+    """rt_denoise_var: the parameters of the variance-guided filter (default_denoise_var())."""
+
+    _fields_ = [
+        ("levels", ctypes.c_int32),
+        ("normal_power", ctypes.c_int32),
+        ("sigma_lum", ctypes.c_double),
+        ("sigma_depth", ctypes.c_double),
+        ("demodulate", ctypes.c_int32),
+        ("prefilter", ctypes.c_int32),
+    ]
+
+
 class Counts(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in COUNT_FIELDS] + [("culled", ctypes.c_uint64 * 9),
                                                                ("soft_occlusion", ctypes.c_uint64 * 9),
@@ -393,6 +432,15 @@ EXPORTED_SYMBOLS = [
     "rt_temporal_default",
     "rt_temporal_async",
     "rt_temporal_host",
+    "rt_temporal_moments_async",
+    "rt_temporal_moments_host",
+    "rt_variance_default",
+    "rt_variance_async",
+    "rt_variance_host",
+    "rt_denoise_var_default",
+    "rt_denoise_var_workspace_bytes",
+    "rt_denoise_var_async",
+    "rt_denoise_var_host",
 ]
 
 _lib = None
@@ -529,6 +577,19 @@ def lib():
                                               ctypes.POINTER(TemporalFrame), vp, vp, vp, vp]),
         "rt_temporal_host": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
                                              ctypes.POINTER(TemporalFrame), vp, vp, vp]),
+        "rt_temporal_moments_async": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
+                                                      ctypes.POINTER(TemporalFrame), vp, vp, vp, vp, vp, vp, vp]),
+        "rt_temporal_moments_host": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
+                                                     ctypes.POINTER(TemporalFrame), vp, vp, vp, vp, vp, vp]),
+        "rt_variance_default": (None, [ctypes.POINTER(Variance)]),
+        "rt_variance_async": (ctypes.c_int, [ctypes.POINTER(Variance), i32, i32, ctypes.POINTER(VarianceInputs), vp, vp]),
+        "rt_variance_host": (ctypes.c_int, [ctypes.POINTER(Variance), i32, i32, ctypes.POINTER(VarianceInputs), vp]),
+        "rt_denoise_var_default": (None, [ctypes.POINTER(DenoiseVar)]),
+        "rt_denoise_var_workspace_bytes": (sz, [i32, i32]),
+        "rt_denoise_var_async": (ctypes.c_int, [ctypes.POINTER(DenoiseVar), i32, i32, ctypes.POINTER(DenoiseInputs), vp,
+                                                 vp, vp, vp, vp, sz, vp]),
+        "rt_denoise_var_host": (ctypes.c_int, [ctypes.POINTER(DenoiseVar), i32, i32, ctypes.POINTER(DenoiseInputs), vp,
+                                                vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -683,6 +744,7 @@ class ParallelRenderer:
         self.last_denoised_linear = None  # the filter's linear output of the last denoised render (H x W x 3)
         self.last_temporal_linear = None  # render_sequence(temporal=...): the accumulated frames (n x H x W x 3)
         self.last_history = None  # ... and each pixel's history length (n x H x W)
+        self.last_variance = None  # variance=...: the variance pass's output (n x H x W, or H x W of render_denoised)
 
     def set_tuning(self, tuning: Tuning):
         self._tuning = tuning
@@ -928,7 +990,7 @@ class ParallelRenderer:
         return img
 
     def render_sequence(self, scene: Scene, width: int, height: int, cameras, seeds=None, temporal=None,
-                        denoise=None) -> np.ndarray:
+                        denoise=None, variance=None) -> np.ndarray:
         """The scene from each of ``cameras`` (Camera structs or scene-file camera dicts; any number):
         an (n, H, W, 4) uint8 array, frame f that of ``render`` with the scene's camera replaced by
         cameras[f] and seed seeds[f] (None: the renderer's seed), byte for byte.
@@ -947,12 +1009,24 @@ class ParallelRenderer:
         with --orbit): frame f's returned image is rt_denoise_async of its accumulated colour with its own
         features; what is fed back to the next frame is the unfiltered accumulation.
         ``last_denoised_linear`` is (n, H, W, 3).  A call without ``temporal`` / ``denoise`` sets the
-        attributes of what it did not compute to None."""
+        attributes of what it did not compute to None.
+
+        variance (True, or a dict of DenoiseVar's and Variance's fields; §4.15; only together with
+        ``temporal`` and instead of ``denoise``, as the CLI's --denoise-variance): the accumulation also
+        carries the luminance moments (rt_temporal_moments_async, the unfiltered accumulation and moments
+        are fed back), rt_variance_async turns them into each frame's variance and frame f's returned image
+        is rt_denoise_var_async of its accumulated colour.  ``last_variance`` is (n, H, W) float32,
+        ``last_denoised_linear`` (n, H, W, 3)."""
         t0 = time.perf_counter()
         tp = None if temporal is None or temporal is False else _as_temporal(temporal)
         dn = None if denoise is None or denoise is False else _as_denoise(denoise)
+        vg = None if variance is None or variance is False else _as_variance(variance)
         if dn is not None and tp is None:
             raise RenderError("render_sequence: denoise filters the accumulated frames and needs temporal")
+        if vg is not None and tp is None:
+            raise RenderError("render_sequence: variance is estimated from the accumulated frames and needs temporal")
+        if vg is not None and dn is not None:
+            raise RenderError("render_sequence: variance and denoise are two filters for the same frames: give one")
         if tp is not None and int(self.settings.samples) < 1:
             raise RenderError("render_sequence: temporal needs settings.samples >= 1")
         if (len(self.devices) if self.devices else max(1, self.settings.num_devices)) > 1:
@@ -997,6 +1071,12 @@ class ParallelRenderer:
                     nbytes = denoise_workspace_bytes(width, height)
                     work = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
                     dlin = torch.zeros((n, npix * 3), dtype=torch.float32, device="cuda")
+                if vg is not None:
+                    nbytes = denoise_var_workspace_bytes(width, height)
+                    work = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+                    dlin = torch.zeros((n, npix * 3), dtype=torch.float32, device="cuda")
+                    mom = torch.zeros((n, npix * 2), dtype=torch.float32, device="cuda")
+                    var = torch.zeros((n, npix), dtype=torch.float32, device="cuda")
                 fst = Settings.from_buffer_copy(self.settings)
                 prev = None
                 for f in range(n):
@@ -1009,8 +1089,20 @@ class ParallelRenderer:
                     cur = temporal_frame(camera_frame(cams[f], int(self.settings.camera), width, height),
                                          lin[f].data_ptr(), ft["depth"].data_ptr(), ft["object"].data_ptr(),
                                          ft["normal"].data_ptr())
-                    temporal_async(width, height, cur, prev, acc[f].data_ptr(), cnt[f].data_ptr(),
-                                   rgba[f].data_ptr(), tp, 0)
+                    if vg is not None:
+                        temporal_moments_async(width, height, cur, prev, ft["albedo"].data_ptr(),
+                                               mom[f - 1].data_ptr() if prev is not None else None, acc[f].data_ptr(),
+                                               cnt[f].data_ptr(), mom[f].data_ptr(), None, tp, 0)
+                        variance_async(width, height, acc[f].data_ptr(), ft["normal"].data_ptr(),
+                                       ft["depth"].data_ptr(), ft["albedo"].data_ptr(), ft["object"].data_ptr(),
+                                       mom[f].data_ptr(), cnt[f].data_ptr(), var[f].data_ptr(), vg[0], 0)
+                        denoise_var_async(width, height, acc[f].data_ptr(), ft["normal"].data_ptr(),
+                                          ft["depth"].data_ptr(), var[f].data_ptr(), ft["albedo"].data_ptr(),
+                                          ft["object"].data_ptr(), dlin[f].data_ptr(), rgba[f].data_ptr(), None,
+                                          work.data_ptr(), nbytes, vg[1], 0)
+                    else:
+                        temporal_async(width, height, cur, prev, acc[f].data_ptr(), cnt[f].data_ptr(),
+                                       rgba[f].data_ptr(), tp, 0)
                     prev = temporal_frame(cur.frame, acc[f].data_ptr(), ft["depth"].data_ptr(),
                                           ft["object"].data_ptr(), ft["normal"].data_ptr(), cnt[f].data_ptr())
                     if dn is not None:
@@ -1021,7 +1113,9 @@ class ParallelRenderer:
             self.last_linear = lin.cpu().numpy().reshape(n, height, width, 3)
             self.last_temporal_linear = acc.cpu().numpy().reshape(n, height, width, 3) if tp is not None else None
             self.last_history = cnt.cpu().numpy().reshape(n, height, width) if tp is not None else None
-            self.last_denoised_linear = dlin.cpu().numpy().reshape(n, height, width, 3) if dn is not None else None
+            self.last_denoised_linear = (dlin.cpu().numpy().reshape(n, height, width, 3)
+                                         if dn is not None or vg is not None else None)
+            self.last_variance = var.cpu().numpy().reshape(n, height, width) if vg is not None else None
             img = rgba.cpu().numpy().reshape(n, height, width, 4)
         self.benchmark_data = {
             "scene_name": "demo_scene",
@@ -1089,12 +1183,17 @@ class ParallelRenderer:
         out_rgba = torch.zeros(npix * 4, dtype=torch.uint8, device="cuda")
         return feat, work, nbytes, out_lin, out_rgba
 
-    def render_denoised(self, scene: Scene, width: int, height: int, params=None, camera=None) -> np.ndarray:
+    def render_denoised(self, scene: Scene, width: int, height: int, params=None, camera=None,
+                        variance=None) -> np.ndarray:
         """Render, then denoise: the frame of ``render`` (the renderer's settings; camera as
         in ``render_aov``), its first-hit feature buffers with the same samples, seed and camera model, and
         rt_denoise_async over both, on the renderer's first device.  params: a Denoise, a dict of its fields
         or None (default_denoise()).  Returns the denoised (H, W, 4) uint8 image; ``last_linear`` is the raw
-        render's linear radiance as after ``render``, ``last_denoised_linear`` the filter's."""
+        render's linear radiance as after ``render``, ``last_denoised_linear`` the filter's.
+
+        variance (True, or a dict of DenoiseVar's and Variance's fields; §4.15; instead of ``params``): the
+        filter is rt_denoise_var_async, steered by rt_variance_async of the render.  A single frame has no
+        moments, so the variance is the spatial estimate; ``last_variance`` is (H, W) float32."""
         if int(width) < 1 or int(height) < 1:
             raise RenderError(f"render_denoised: invalid image size {width}x{height}")
         if int(self.settings.samples) < 1:
@@ -1103,6 +1202,9 @@ class ParallelRenderer:
             raise RenderError("render_denoised: a camera dict needs a position")
         if camera is not None and not isinstance(camera, (dict, Camera, Scene)):
             raise RenderError("render_denoised: camera is a Camera, a Scene, a camera dict or None")
+        vg = None if variance is None or variance is False else _as_variance(variance)
+        if vg is not None and params is not None:
+            raise RenderError("render_denoised: variance and params are two filters for the same frame: give one")
         dn = _as_denoise(params)
         view = SceneView.from_buffer_copy(scene.view)  # (validated with the camera the frame is shot from)
         if camera is not None:
@@ -1129,10 +1231,22 @@ class ParallelRenderer:
                                  AovBuffers(feat["albedo"].data_ptr(), feat["normal"].data_ptr(),
                                             feat["depth"].data_ptr(), None, feat["object"].data_ptr()),
                                  camera=camera, stream=0)
-            denoise_async(width, height, lin.data_ptr(), feat["normal"].data_ptr(), feat["depth"].data_ptr(),
-                          feat["albedo"].data_ptr(), feat["object"].data_ptr(), out_lin.data_ptr(),
-                          out_rgba.data_ptr(), work.data_ptr(), nbytes, dn, 0)
+            if vg is not None:
+                nbytes = denoise_var_workspace_bytes(width, height)
+                work = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+                var = torch.zeros(npix, dtype=torch.float32, device="cuda")
+                variance_async(width, height, lin.data_ptr(), feat["normal"].data_ptr(), feat["depth"].data_ptr(),
+                               feat["albedo"].data_ptr(), feat["object"].data_ptr(), None, None, var.data_ptr(),
+                               vg[0], 0)
+                denoise_var_async(width, height, lin.data_ptr(), feat["normal"].data_ptr(), feat["depth"].data_ptr(),
+                                  var.data_ptr(), feat["albedo"].data_ptr(), feat["object"].data_ptr(),
+                                  out_lin.data_ptr(), out_rgba.data_ptr(), None, work.data_ptr(), nbytes, vg[1], 0)
+            else:
+                denoise_async(width, height, lin.data_ptr(), feat["normal"].data_ptr(), feat["depth"].data_ptr(),
+                              feat["albedo"].data_ptr(), feat["object"].data_ptr(), out_lin.data_ptr(),
+                              out_rgba.data_ptr(), work.data_ptr(), nbytes, dn, 0)
             torch.cuda.synchronize()
+            self.last_variance = var.cpu().numpy().reshape(height, width) if vg is not None else None
             self.last_linear = lin.cpu().numpy().reshape(height, width, 3)
             self.last_denoised_linear = out_lin.cpu().numpy().reshape(height, width, 3)
             return out_rgba.cpu().numpy().reshape(height, width, 4)
@@ -1595,6 +1709,190 @@ def temporal_host(cur: dict, prev=None, params=None):
     _check(lib().rt_temporal_host(ctypes.byref(p), w, h, ctypes.byref(fc), ctypes.byref(fp) if fp is not None else None,
                                   out.ctypes.data, cnt.ctypes.data, rgba.ctypes.data))
     return out, cnt, rgba
+
+
+_VARIANCE_FIELDS = ("min_history", "normal_power", "sigma_depth")
+_DENOISE_VAR_FIELDS = ("levels", "normal_power", "sigma_lum", "sigma_depth", "demodulate", "prefilter")
+
+
+def default_variance(**over) -> Variance:
+    """rt_variance_default (min_history 4, normal_power 32, sigma_depth 0.05), with the given fields replaced."""
+    v = Variance()
+    lib().rt_variance_default(ctypes.byref(v))
+    for k, val in over.items():
+        if k not in _VARIANCE_FIELDS:
+            raise RenderError(f"default_variance: no such field {k}")
+        setattr(v, k, val)
+    return v
+
+
+def default_denoise_var(**over) -> DenoiseVar:
+    """rt_denoise_var_default (levels 4, normal_power 32, sigma_lum 2, sigma_depth 0.05, demodulate 1,
+    prefilter 1), with the given fields replaced."""
+    d = DenoiseVar()
+    lib().rt_denoise_var_default(ctypes.byref(d))
+    for k, val in over.items():
+        if k not in _DENOISE_VAR_FIELDS:
+            raise RenderError(f"default_denoise_var: no such field {k}")
+        setattr(d, k, val)
+    return d
+
+
+def _as_one(params, cls, default, what):
+    if params is None or params is True:
+        return default()
+    if isinstance(params, cls):
+        return params
+    if isinstance(params, dict):
+        return default(**params)
+    raise RenderError(f"{what} parameters are a {cls.__name__}, a dict of its fields or None")
+
+
+def _as_variance(params):
+    """The (Variance, DenoiseVar) of a ``variance=`` argument.  True: the defaults; a dict: each field goes
+    to the struct that has it (normal_power and sigma_depth to both); a (Variance, DenoiseVar) pair as it is."""
+    if params is True:
+        return default_variance(), default_denoise_var()
+    if isinstance(params, tuple) and len(params) == 2 and isinstance(params[0], Variance) \
+            and isinstance(params[1], DenoiseVar):
+        return params
+    if isinstance(params, dict):
+        for k in params:
+            if k not in _VARIANCE_FIELDS and k not in _DENOISE_VAR_FIELDS:
+                raise RenderError(f"variance: no such field {k}")
+        return (default_variance(**{k: v for k, v in params.items() if k in _VARIANCE_FIELDS}),
+                default_denoise_var(**{k: v for k, v in params.items() if k in _DENOISE_VAR_FIELDS}))
+    raise RenderError("variance is True, a dict of DenoiseVar's and Variance's fields or a (Variance, DenoiseVar) pair")
+
+
+def temporal_moments_async(width: int, height: int, cur: TemporalFrame, prev, d_cur_albedo, d_prev_moments,
+                           d_out_color: int, d_out_count: int, d_out_moments: int, d_out_rgba=None, params=None,
+                           stream: int = 0):
+    """rt_temporal_moments_async: temporal_async with the current frame's albedo (None:
+    not given), the previous call's moments (given exactly when prev is) and the moments' output, all
+    device pointers.  The three outputs must not be prev's color / count / moments."""
+    p = _as_temporal(params)
+    _check(lib().rt_temporal_moments_async(ctypes.byref(p), width, height, ctypes.byref(cur),
+                                           ctypes.byref(prev) if prev is not None else None,
+                                           ctypes.c_void_p(d_cur_albedo), ctypes.c_void_p(d_prev_moments),
+                                           ctypes.c_void_p(d_out_color), ctypes.c_void_p(d_out_count),
+                                           ctypes.c_void_p(d_out_moments), ctypes.c_void_p(d_out_rgba),
+                                           ctypes.c_void_p(stream)))
+
+
+def _host_arrays(what, h, w, keep, **arrays):
+    """Contiguous arrays of the expected (dtype, shape), kept alive in ``keep``; returns their addresses."""
+    out = {}
+    for name, (a, dtype, shape) in arrays.items():
+        if a is None:
+            out[name] = None
+            continue
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape != shape:
+            raise RenderError(f"{what}: {name} has shape {a.shape}, expected {shape}")
+        keep.append(a)
+        out[name] = a.ctypes.data
+    return out
+
+
+def temporal_moments_host(cur: dict, prev=None, params=None):
+    """rt_temporal_moments_host: temporal_host with the luminance moments.  cur may also hold ``albedo``
+    (H, W, 3) float32, prev must also hold ``moments`` (H, W, 2) float32 -- the previous call's.  Returns
+    (color, count, moments (H, W, 2) float32, rgba)."""
+    color = np.ascontiguousarray(cur["color"], np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise RenderError("temporal_moments_host: color is an (H, W, 3) array")
+    h, w = color.shape[:2]
+    keep = []
+
+    def frame_of(d, name):
+        a = _host_arrays(f"temporal_moments_host: {name}", h, w, keep,
+                         color=(d.get("color"), np.float32, (h, w, 3)), depth=(d.get("depth"), np.float32, (h, w)),
+                         object=(d.get("object"), np.int32, (h, w)), normal=(d.get("normal"), np.float32, (h, w, 3)),
+                         count=(d.get("count"), np.float32, (h, w)), albedo=(d.get("albedo"), np.float32, (h, w, 3)),
+                         moments=(d.get("moments"), np.float32, (h, w, 2)))
+        return temporal_frame(d["frame"], a["color"], a["depth"], a["object"], a["normal"], a["count"]), a
+
+    fc, ac = frame_of(cur, "cur")
+    fp, ap = frame_of(prev, "prev") if prev is not None else (None, {"moments": None})
+    p = _as_temporal(params)
+    out = np.zeros((h, w, 3), np.float32)
+    cnt = np.zeros((h, w), np.float32)
+    mom = np.zeros((h, w, 2), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    _check(lib().rt_temporal_moments_host(ctypes.byref(p), w, h, ctypes.byref(fc),
+                                          ctypes.byref(fp) if fp is not None else None, ac["albedo"], ap["moments"],
+                                          out.ctypes.data, cnt.ctypes.data, mom.ctypes.data, rgba.ctypes.data))
+    return out, cnt, mom, rgba
+
+
+def variance_async(width: int, height: int, d_color: int, d_normal: int, d_depth: int, d_albedo=None, d_object=None,
+                   d_moments=None, d_count=None, d_out_var: int = None, params=None, stream: int = 0):
+    """rt_variance_async (DESIGN.md §4.15): every argument a device pointer (an int; None: not given);
+    d_moments and d_count both or neither; asynchronous on ``stream``."""
+    p = _as_one(params, Variance, default_variance, "variance")
+    inp = VarianceInputs(d_color, d_normal, d_depth, d_albedo, d_object, d_moments, d_count)
+    _check(lib().rt_variance_async(ctypes.byref(p), width, height, ctypes.byref(inp), ctypes.c_void_p(d_out_var),
+                                   ctypes.c_void_p(stream)))
+
+
+def variance_host(color, normal, depth, albedo=None, object=None, moments=None, count=None, params=None):
+    """rt_variance_host: the variance pass on numpy arrays, without a device.  moments is (H, W, 2) float32,
+    count (H, W) float32.  Returns the variance, (H, W) float32."""
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise RenderError("variance_host: color is an (H, W, 3) array")
+    h, w = color.shape[:2]
+    keep = []
+    a = _host_arrays("variance_host", h, w, keep, color=(color, np.float32, (h, w, 3)),
+                     normal=(normal, np.float32, (h, w, 3)), depth=(depth, np.float32, (h, w)),
+                     albedo=(albedo, np.float32, (h, w, 3)), object=(object, np.int32, (h, w)),
+                     moments=(moments, np.float32, (h, w, 2)), count=(count, np.float32, (h, w)))
+    p = _as_one(params, Variance, default_variance, "variance")
+    inp = VarianceInputs(*[a[k] for k in ("color", "normal", "depth", "albedo", "object", "moments", "count")])
+    out = np.zeros((h, w), np.float32)
+    _check(lib().rt_variance_host(ctypes.byref(p), w, h, ctypes.byref(inp), out.ctypes.data))
+    return out
+
+
+def denoise_var_workspace_bytes(width: int, height: int) -> int:
+    """rt_denoise_var_workspace_bytes: the device bytes rt_denoise_var_async needs for a width x height image."""
+    return int(lib().rt_denoise_var_workspace_bytes(width, height))
+
+
+def denoise_var_async(width: int, height: int, d_color: int, d_normal: int, d_depth: int, d_variance: int,
+                      d_albedo=None, d_object=None, d_out_linear=None, d_out_rgba=None, d_out_variance=None,
+                      d_workspace=None, workspace_bytes: int = 0, params=None, stream: int = 0):
+    """rt_denoise_var_async (DESIGN.md §4.15): every argument a device pointer (an int; None: not given);
+    asynchronous on ``stream``."""
+    p = _as_one(params, DenoiseVar, default_denoise_var, "denoise_var")
+    inp = DenoiseInputs(d_color, d_normal, d_depth, d_albedo, d_object)
+    _check(lib().rt_denoise_var_async(ctypes.byref(p), width, height, ctypes.byref(inp), ctypes.c_void_p(d_variance),
+                                      ctypes.c_void_p(d_out_linear), ctypes.c_void_p(d_out_rgba),
+                                      ctypes.c_void_p(d_out_variance), ctypes.c_void_p(d_workspace), workspace_bytes,
+                                      ctypes.c_void_p(stream)))
+
+
+def denoise_var_host(color, normal, depth, variance, albedo=None, object=None, params=None):
+    """rt_denoise_var_host: the variance-guided filter on numpy arrays, without a device.  variance is
+    (H, W) float32.  Returns (linear (H, W, 3) float32, rgba (H, W, 4) uint8, variance (H, W) float32)."""
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise RenderError("denoise_var_host: color is an (H, W, 3) array")
+    h, w = color.shape[:2]
+    keep = []
+    a = _host_arrays("denoise_var_host", h, w, keep, color=(color, np.float32, (h, w, 3)),
+                     normal=(normal, np.float32, (h, w, 3)), depth=(depth, np.float32, (h, w)),
+                     albedo=(albedo, np.float32, (h, w, 3)), object=(object, np.int32, (h, w)),
+                     variance=(variance, np.float32, (h, w)))
+    p = _as_one(params, DenoiseVar, default_denoise_var, "denoise_var")
+    inp = DenoiseInputs(*[a[k] for k in ("color", "normal", "depth", "albedo", "object")])
+    lin = np.zeros((h, w, 3), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    var = np.zeros((h, w), np.float32)
+    _check(lib().rt_denoise_var_host(ctypes.byref(p), w, h, ctypes.byref(inp), a["variance"], lin.ctypes.data,
+                                     rgba.ctypes.data, var.ctypes.data))
+    return lin, rgba, var
 
 
 def max_local_tiles(width: int, height: int, world: int) -> int:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async, rt_denoise, rt_denoise_inputs, rt_denoise_default, rt_denoise_workspace_bytes, rt_denoise_async, rt_denoise_host, rt_temporal, rt_temporal_frame, rt_temporal_default, rt_temporal_async, rt_temporal_host); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async, rt_denoise, rt_denoise_inputs, rt_denoise_default, rt_denoise_workspace_bytes, rt_denoise_async, rt_denoise_host, rt_temporal, rt_temporal_frame, rt_temporal_default, rt_temporal_async, rt_temporal_host, rt_temporal_moments_async / _host, rt_variance, rt_variance_inputs, rt_variance_default, rt_variance_async / _host, rt_denoise_var, rt_denoise_var_default, rt_denoise_var_workspace_bytes, rt_denoise_var_async / _host); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -852,6 +852,146 @@ int rt_temporal_async(const rt_temporal* params, int32_t width, int32_t height, 
                       float* d_out_count, uint8_t* d_out_rgba /* may be NULL */, void* hip_stream);
 int rt_temporal_host(const rt_temporal* params, int32_t width, int32_t height, const rt_temporal_frame* cur,
                      const rt_temporal_frame* prev, float* out_color, float* out_count, uint8_t* out_rgba);
+
+/* Variance-guided denoising: temporal accumulation also
+ * gathers the first two moments of the demodulated luminance, a variance pass
+ * turns them into the per-pixel variance of the accumulated colour, and a
+ * second à-trous filter scales its luminance stop by that variance, pixel by
+ * pixel.  A pixel whose frames agree (a static reflection, a sharp shadow
+ * edge) has a low variance and keeps its detail; one whose frames disagree
+ * (soft-shadow and bounce noise) is smoothed.  Three calls beside
+ * rt_temporal_async and rt_denoise_async, which stay what they are; all three
+ * trace no ray and are defined to the bit like those: binary64 `+ - * /`,
+ * comparisons and floor only, in one written order, floats widened before use
+ * and rounded once on store (include/rt_variance.h is the code the kernels and
+ * the _host twins run).  No address depends on a pixel's value, so non-finite
+ * colours, moments and variances, zero normals and depth <= 0 cannot fault;
+ * their values carry no contract.
+ *
+ * Common definitions, all in binary64:
+ *   floor(a)    = a > 2^-6 ? a : 2^-6                      (rt_denoise_async's)
+ *   e(c, a)[k]  = albedo given ? (double)c[k] / floor((double)a[k]) : (double)c[k]
+ *                 (not rounded to binary32 in between)
+ *   lum(e)      = (0.2126 * e0 + 0.7152 * e1) + 0.0722 * e2
+ *   valid(p)    : depth[p] is finite
+ *
+ * 1. rt_temporal_moments_async: rt_temporal_async with three more buffers,
+ *      cur_albedo    float3  optional: the current frame's albedo (NULL: lum of the colour itself)
+ *      prev_moments  float2  required exactly when prev is given: the PREVIOUS CALL's out_moments
+ *      out_moments   float2  required
+ *    out_color, out_count and out_rgba are rt_temporal_async's, bit for bit, for
+ *    every input: its steps 1 to 7 in its order.  Per pixel p,
+ *    l = lum(e(cur.color[p], cur_albedo[p])) and mcur = (l, l * l).  Where step
+ *    5 accepts a tap q with weight w it also continues
+ *    summ[j] += w * (double)prev_moments[q][j] (j = 0, 1; after sumn), and where
+ *    step 6 finds a history, hm[j] = summ[j] / sumw and
+ *    out_moments[j] = (float)(hm[j] + (mcur[j] - hm[j]) / n1) with step 6's n1.
+ *    In every other case (p not valid, prev NULL, no history)
+ *    out_moments = ((float)l, (float)(l * l)).
+ *    Refused like rt_temporal_async, and also: prev given without prev_moments
+ *    or prev_moments without prev; a NULL out_moments; out_moments ==
+ *    prev_moments (the third ping-pong pair).
+ *
+ * 2. rt_variance_async: the variance of the accumulated demodulated luminance.
+ *    Inputs (rt_variance_inputs): color (the accumulated colour), normal and
+ *    depth required; albedo and object optional; moments (float2) and count
+ *    optional, both or neither.  Parameters (rt_variance; rt_variance_default):
+ *      min_history   >= 1, finite                          default 4
+ *      normal_power  0 (off) or a power of two <= 128      default 32
+ *      sigma_depth   >= 0, finite; 0: off                  default 0.05
+ *    Per pixel p, out_var[p] is
+ *      0 when p is not valid; otherwise, with
+ *      n = count given ? ((double)count[p] > 1 ? (double)count[p] : 1) : 1:
+ *      temporal (moments given and (double)count[p] >= min_history):
+ *        v = m2 - m1 * m1 with (m1, m2) = moments[p]; v = v > 0 ? v : 0;
+ *        out_var = (float)(v / n).
+ *      spatial (otherwise): sumw, s1, s2 start at 0; the 49 taps q = (x + dx,
+ *        y + dy) with dy = -3..3 in the outer and dx = -3..3 in the inner loop.
+ *        A tap is skipped when q is outside the image, not valid, or object is
+ *        given and object[q] != object[p].  Otherwise w = 1, then steps 2 and 3
+ *        of rt_denoise_async's tap weight (normal, depth) on w;
+ *        (m1q, m2q) = moments[q] when moments is given, else lq = lum(e(color[q],
+ *        albedo[q])) and (lq, lq * lq); s1 += w * m1q, s2 += w * m2q, sumw += w.
+ *        Then a = s1 / sumw, v = s2 / sumw - a * a, v = v > 0 ? v : 0 and
+ *        out_var = sumw > 0 ? (float)(v / n) : 0.
+ *    The division by n makes it the variance of the MEAN of n samples; where
+ *    the history is shorter than min_history the neighbourhood stands in for it.
+ *
+ * 3. rt_denoise_var_async: rt_denoise_async's inputs plus variance (float,
+ *    required).  Parameters (rt_denoise_var; rt_denoise_var_default):
+ *      levels, normal_power, sigma_depth, demodulate   as rt_denoise
+ *      sigma_lum   >= 0, finite; 0: the luminance stop is off   default 2
+ *      prefilter   0 or 1                                       default 1
+ *    Prepare, the 25 taps and their order, the skip rules, steps 1 to 3 and 5,
+ *    the sumw > 0 rule, remodulation, the tone map and the in-place rule are
+ *    rt_denoise_async's.  The differences: every pixel carries var_i(p), with
+ *    var_0 = variance.  Per level i and valid p, when sigma_lum > 0:
+ *      g = (double)var_i(p) without the prefilter.  With it, sumg = sumk = 0,
+ *        then the 9 taps q = (x + dx, y + dy) -- step 1 at every level -- with
+ *        dy = -1..1 outer and dx = -1..1 inner, skipped by the same rules,
+ *        k = {1/4, 1/8, 1/16}[|dx| + |dy|], sumg += k * (double)var_i(q),
+ *        sumk += k; g = sumg / sumk.
+ *      inv = 1 / ((sigma_lum * sigma_lum) * g + 2^-40), once per pixel.
+ *    Step 4 becomes: if sigma_lum > 0, d = lum(e_i(q)) - lum(e_i(p)) (the
+ *    binary32 records widened) and w = w / (1 + (d * d) * inv).  Step 5 also
+ *    continues sumv += (w * w) * (double)var_i(q) (after sum[2]), and
+ *    var_{i+1}(p) = sumw > 0 ? (float)(sumv / (sumw * sumw)) : var_i(p); a pixel
+ *    that is not valid keeps var_i(p).  Outputs: d_out_linear and d_out_rgba as
+ *    rt_denoise_async's (either may be NULL, not both); d_out_variance, if
+ *    given, is var_levels.  out_linear == color and out_variance == variance
+ *    (in place) are allowed; any other overlap carries no contract.
+ *    With sigma_lum = 0 the colour is rt_denoise_async's with sigma_color = 0,
+ *    bit for bit.
+ *
+ * Calls.  Every buffer pointer of an _async call is a DEVICE pointer of the
+ * current device; the structs are read before the call returns; the calls are
+ * asynchronous on `hip_stream`, take no context and allocate nothing.  The
+ * moments and the variance pass need no workspace; the caller owns the
+ * filter's (rt_denoise_var_workspace_bytes(w, h) bytes at least, at most
+ * 64 * w * h + 256; 0 for a size rt_validate refuses).  RT_E_INVALID with a
+ * message, nothing enqueued and no buffer touched: what is listed above; NULL
+ * params or inputs; a NULL required buffer; a size that rt_validate refuses;
+ * parameters out of range, NaN included; a NULL or too small workspace.  The
+ * _host twins do the same with host pointers and no device. */
+typedef struct { double min_history; double sigma_depth; int32_t normal_power; int32_t _pad; } rt_variance;
+typedef struct {
+  const float* color;     /* W*H*3, required */
+  const float* normal;    /* W*H*3, required */
+  const float* depth;     /* W*H,   required */
+  const float* albedo;    /* W*H*3 or NULL */
+  const int32_t* object;  /* W*H   or NULL */
+  const float* moments;   /* W*H*2 or NULL */
+  const float* count;     /* W*H   or NULL: given exactly when moments is */
+} rt_variance_inputs;
+typedef struct {
+  int32_t levels;
+  int32_t normal_power;
+  double sigma_lum;
+  double sigma_depth;
+  int32_t demodulate;
+  int32_t prefilter;
+} rt_denoise_var;
+int rt_temporal_moments_async(const rt_temporal* params, int32_t width, int32_t height, const rt_temporal_frame* cur,
+                              const rt_temporal_frame* prev /* NULL: start a history */,
+                              const float* d_cur_albedo /* may be NULL */, const float* d_prev_moments,
+                              float* d_out_color, float* d_out_count, float* d_out_moments,
+                              uint8_t* d_out_rgba /* may be NULL */, void* hip_stream);
+int rt_temporal_moments_host(const rt_temporal* params, int32_t width, int32_t height, const rt_temporal_frame* cur,
+                             const rt_temporal_frame* prev, const float* cur_albedo, const float* prev_moments,
+                             float* out_color, float* out_count, float* out_moments, uint8_t* out_rgba);
+void rt_variance_default(rt_variance* v);
+int rt_variance_async(const rt_variance* params, int32_t width, int32_t height, const rt_variance_inputs* in,
+                      float* d_out_var, void* hip_stream);
+int rt_variance_host(const rt_variance* params, int32_t width, int32_t height, const rt_variance_inputs* in,
+                     float* out_var);
+void rt_denoise_var_default(rt_denoise_var* d);
+size_t rt_denoise_var_workspace_bytes(int32_t width, int32_t height);
+int rt_denoise_var_async(const rt_denoise_var* params, int32_t width, int32_t height, const rt_denoise_inputs* in,
+                         const float* d_variance, float* d_out_linear, uint8_t* d_out_rgba,
+                         float* d_out_variance /* may be NULL */, void* d_workspace, size_t workspace_bytes,
+                         void* hip_stream);
+int rt_denoise_var_host(const rt_denoise_var* params, int32_t width, int32_t height, const rt_denoise_inputs* in,
+                        const float* variance, float* out_linear, uint8_t* out_rgba, float* out_variance);
 
 /* What a context has done so far (diagnostics): work schedules built (a new
  * scene, frame, rank or settings key; a measured re-cut counts too),
