@@ -356,8 +356,10 @@ __global__ __launch_bounds__(64) void sched_blocks(const SchedParams p) {
   }
   {
     double a = excl;
-    int nb = lane + 1 < 64 ? __shfl_down(sbig, 1) : 1024;
-    if (lane == 63) nb = 1024;
+    // (the shuffle outside the condition: under `lane + 1 < 64 ? __shfl_down(..) : ..` lane 63 sat out of it,
+    // lane 62 read an inactive lane's 0, and every block that reached pixels 992..1007 ended after one pixel)
+    const int above = __shfl_down(sbig, 1);
+    int nb = lane + 1 < 64 ? above : 1024;
     for (int k = 15; k >= 0; --k) {
       if (v[k] > bw || heavy_of(q0 + k)) nb = q0 + k;
       s_big[q0 + k] = (uint16_t)nb;
