@@ -10,6 +10,7 @@
 //             [--denoise default|LEVELS[,SIGMA_COLOR[,SIGMA_DEPTH[,NORMAL_POWER]]]]
 //             [--temporal default|MAX_HISTORY[,DEPTH_TOL[,NORMAL_MIN]]]
 //             [--denoise-variance default|LEVELS[,SIGMA_LUM[,SIGMA_DEPTH[,NORMAL_POWER]]]]
+//             [--aov-specular default|BOUNCES[,MAX_ROUGHNESS]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -77,6 +78,18 @@
 // (rt_denoise_var_default, rt_variance_default) or up to four comma-separated
 // fields that replace the defaults from the left; SIGMA_DEPTH and NORMAL_POWER
 // go to the variance pass too.
+// --aov-specular SPEC (with --aov, --denoise or
+// --denoise-variance) makes the run's feature pass the specular-through one
+// (rt_context_render_aov_spec_async): ideal mirror reflections are followed
+// from each first hit, at most BOUNCES (0..16) of them, through metal, shiny
+// and perfectmirror surfaces whose roughness is at most MAX_ROUGHNESS.  SPEC
+// is `default` (rt_aov_spec_default: 4, 0.1).  --aov then writes SEVEN images:
+// the five above taken behind the mirrors, PREFIX.specular (grey
+// round(s * 255)) and PREFIX.bounces (grey round(clamp01(b / BOUNCES) * 255),
+// black for BOUNCES 0).  --denoise and --denoise-variance guide their filter by
+// the specular-through albedo, normal, depth and object; with --orbit
+// --temporal the accumulation keeps the first-hit buffers (reprojection needs
+// the geometric depth) and only the spatial filter changes its guide.
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
@@ -337,6 +350,21 @@ struct VarianceSpec {
   rt_denoise_var dv;
   rt_variance vr;
 };
+// --aov-specular: the run's feature pass is the specular-through one.  The guide a
+// filter reads -- albedo, normal, depth, object -- comes from guide_pass: rt_context_render_aov_spec_async
+// with these parameters when the flag is given, else the first-hit pass.
+static bool g_spec_on = false;
+static rt_aov_spec g_spec;
+static int guide_pass(rt_context* ctx, int32_t w, int32_t h, const rt_settings* st, const rt_camera* cam, float* albedo,
+                      float* normal, float* depth, int32_t* object) {
+  if (g_spec_on) {
+    const rt_aov_spec_buffers out = {albedo, normal, depth, nullptr, object, nullptr, nullptr};
+    return rt_context_render_aov_spec_async(ctx, w, h, st, cam, &g_spec, &out, nullptr);
+  }
+  const rt_aov_buffers out = {albedo, normal, depth, nullptr, object};
+  return rt_context_render_aov_async(ctx, w, h, st, cam, &out, nullptr);
+}
+
 template <class Save>
 static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int n, double degrees,
                         Save save, rt_stats* stats, const rt_temporal* tp = nullptr, const rt_denoise* dn = nullptr,
@@ -372,6 +400,10 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
   const size_t work_bytes = dn ? rt_denoise_workspace_bytes(w, h) : vs ? rt_denoise_var_workspace_bytes(w, h) : 0;
   if (rc == RT_OK && tp && hip_ok(hipMalloc((void**)&d_tp, 2 * set_floats * sizeof(float)), "hipMalloc") && (dn || vs))
     hip_ok(hipMalloc(&d_work, work_bytes), "hipMalloc");
+  // --aov-specular: the spatial filter's guide (albedo | normal | depth | object) beside the first-hit set,
+  // which the accumulation keeps (reprojection needs the geometric depth)
+  float* d_sg = nullptr;
+  if (rc == RT_OK && tp && (dn || vs) && g_spec_on) hip_ok(hipMalloc((void**)&d_sg, npix * 8 * sizeof(float)), "hipMalloc");
   const float* prev_moments = nullptr;
   std::vector<uint64_t> seeds((size_t)n);
   for (int f = 0; f < n; ++f) seeds[(size_t)f] = st.seed + (uint64_t)f;
@@ -402,15 +434,23 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
       rt_temporal_frame cur = {lin[f], depth, object, normal, nullptr, {0}};
       if (rc == RT_OK) rc = rt_camera_frame(&cams[(size_t)(f0 + f)], st.camera, w, h, cur.frame);
       float *mom = set + npix * 12, *var = set + npix * 14;  // (only with vs)
+      const float *g_albedo = albedo, *g_normal = normal, *g_depth = depth;  // the spatial filter's guide
+      const int32_t* g_object = object;
+      if (rc == RT_OK && d_sg) {
+        rc = guide_pass(ctx, w, h, &fst, &cams[(size_t)(f0 + f)], d_sg, d_sg + npix * 3, d_sg + npix * 6,
+                        (int32_t*)(d_sg + npix * 7));
+        g_albedo = d_sg, g_normal = d_sg + npix * 3, g_depth = d_sg + npix * 6;
+        g_object = (const int32_t*)(d_sg + npix * 7);
+      }
       if (rc == RT_OK && !vs)
         rc = rt_temporal_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, acc, cnt, img[f], nullptr);
       if (rc == RT_OK && vs) {
         rc = rt_temporal_moments_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, albedo, prev_moments, acc, cnt,
                                        mom, nullptr, nullptr);
         prev_moments = mom;
-        const rt_variance_inputs vin = {acc, normal, depth, albedo, object, mom, cnt};
+        const rt_variance_inputs vin = {acc, g_normal, g_depth, g_albedo, g_object, mom, cnt};
         if (rc == RT_OK) rc = rt_variance_async(&vs->vr, w, h, &vin, var, nullptr);
-        const rt_denoise_inputs in = {acc, normal, depth, albedo, object};
+        const rt_denoise_inputs in = {acc, g_normal, g_depth, g_albedo, g_object};
         if (rc == RT_OK)
           rc = rt_denoise_var_async(&vs->dv, w, h, &in, var, nullptr, img[f], nullptr, d_work, work_bytes, nullptr);
       }
@@ -418,7 +458,7 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
       prev_frame.color = acc;
       prev_frame.count = cnt;
       if (rc == RT_OK && dn) {
-        const rt_denoise_inputs in = {acc, normal, depth, albedo, object};
+        const rt_denoise_inputs in = {acc, g_normal, g_depth, g_albedo, g_object};
         rc = rt_denoise_async(dn, w, h, &in, nullptr, img[f], d_work, work_bytes, nullptr);
       }
     }
@@ -431,7 +471,7 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
   }
   const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - save_s;
-  for (void* p : {(void*)d_lin, (void*)d_img, (void*)d_tp, d_work})
+  for (void* p : {(void*)d_lin, (void*)d_img, (void*)d_tp, (void*)d_sg, d_work})
     if (p) (void)hipFree(p);
   rt_context_destroy(ctx);
   if (rc != RT_OK) {
@@ -463,18 +503,24 @@ static int write_aov(const rt_scene* scene, int32_t w, int32_t h, const rt_setti
   int rc = rt_context_create(0, &ctx);
   if (rc != RT_OK) return rc;
   rc = rt_context_set_scene(ctx, scene, 0);
-  // one device block: albedo | normal | depth | coverage | object
+  // one device block: albedo | normal | depth | coverage | object | specular | bounces (the last two with
+  // --aov-specular only)
   float* d = nullptr;
-  std::vector<float> host(npix * 9);
-  if (rc == RT_OK && hipMalloc((void**)&d, npix * 9 * sizeof(float)) != hipSuccess) {
+  std::vector<float> host(npix * 11);
+  if (rc == RT_OK && hipMalloc((void**)&d, npix * 11 * sizeof(float)) != hipSuccess) {
     fprintf(stderr, "hipMalloc failed\n");
     rc = RT_E_DEVICE;
   }
-  if (rc == RT_OK) {
+  if (rc == RT_OK && g_spec_on) {
+    const rt_aov_spec_buffers out = {d, d + npix * 3, d + npix * 6, d + npix * 7, (int32_t*)(d + npix * 8),
+                                     d + npix * 9, d + npix * 10};
+    rc = rt_context_render_aov_spec_async(ctx, w, h, &st, nullptr, &g_spec, &out, nullptr);
+  } else if (rc == RT_OK) {
     const rt_aov_buffers out = {d, d + npix * 3, d + npix * 6, d + npix * 7, (int32_t*)(d + npix * 8)};
     rc = rt_context_render_aov_async(ctx, w, h, &st, nullptr, &out, nullptr);
   }
-  if (rc == RT_OK && hipMemcpy(host.data(), d, npix * 9 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+  if (rc == RT_OK && hipMemcpy(host.data(), d, npix * (g_spec_on ? 11 : 9) * sizeof(float), hipMemcpyDeviceToHost) !=
+                         hipSuccess) {
     fprintf(stderr, "hipMemcpy failed\n");
     rc = RT_E_DEVICE;
   }
@@ -495,8 +541,9 @@ static int write_aov(const rt_scene* scene, int32_t w, int32_t h, const rt_setti
       far = std::max(far, (double)depth[i]);
     }
   std::vector<uint8_t> img(npix * 4);
-  const char* names[5] = {"albedo", "normal", "depth", "coverage", "object"};
-  for (int k = 0; k < 5; ++k) {
+  const float *specular = albedo + npix * 9, *bounces = albedo + npix * 10;
+  const char* names[7] = {"albedo", "normal", "depth", "coverage", "object", "specular", "bounces"};
+  for (int k = 0; k < (g_spec_on ? 7 : 5); ++k) {
     for (size_t i = 0; i < npix; ++i) {
       uint8_t* px = &img[4 * i];
       px[3] = 255;
@@ -510,6 +557,10 @@ static int write_aov(const rt_scene* scene, int32_t w, int32_t h, const rt_setti
         px[0] = px[1] = px[2] = g;
       } else if (k == 3) {
         px[0] = px[1] = px[2] = aov_byte(coverage[i]);
+      } else if (k == 5) {
+        px[0] = px[1] = px[2] = aov_byte(specular[i]);
+      } else if (k == 6) {  // grey bounces / max_bounces (max_bounces 0: bounces is 0 everywhere)
+        px[0] = px[1] = px[2] = g_spec.max_bounces > 0 ? aov_byte((double)bounces[i] / g_spec.max_bounces) : 0;
       } else {
         // a fixed colour per hittable index: the bytes of (index + 1) * 2654435761 mod 2^32,
         // each with its top bit set (never black); a miss is black
@@ -559,8 +610,7 @@ static int denoise_image(const rt_scene* scene, int32_t w, int32_t h, const rt_s
   if (rc == RT_OK) {
     rt_settings fst = st;
     fst.samples = feature_samples;
-    const rt_aov_buffers out = {d + npix * 3, d + npix * 6, d + npix * 9, nullptr, (int32_t*)(d + npix * 10)};
-    rc = rt_context_render_aov_async(ctx, w, h, &fst, nullptr, &out, nullptr);
+    rc = guide_pass(ctx, w, h, &fst, nullptr, d + npix * 3, d + npix * 6, d + npix * 9, (int32_t*)(d + npix * 10));
   }
   if (rc == RT_OK) {
     const rt_denoise_inputs in = {d, d + npix * 6, d + npix * 9, d + npix * 3, (const int32_t*)(d + npix * 10)};
@@ -785,6 +835,28 @@ int main(int argc, char** argv) {
         fprintf(stderr, "invalid --aov (a file name prefix)\n");
         return 2;
       }
+    } else if (a == "--aov-specular") {  // the feature pass follows mirrors
+      const std::string x = need("--aov-specular");
+      rt_aov_spec_default(&g_spec);
+      bool ok = !x.empty();
+      if (ok && x != "default") {
+        const size_t comma = x.find(',');
+        ok = parse_int(x.substr(0, comma).c_str(), &v) && v >= 0 && v <= 16;
+        if (ok) g_spec.max_bounces = (int32_t)v;
+        if (ok && comma != std::string::npos) {
+          char* end = nullptr;
+          errno = 0;
+          g_spec.max_roughness = strtod(x.c_str() + comma + 1, &end);
+          ok = end && end != x.c_str() + comma + 1 && *end == 0 && errno == 0 && std::isfinite(g_spec.max_roughness) &&
+               g_spec.max_roughness >= 0;
+        }
+      }
+      if (!ok) {
+        fprintf(stderr, "invalid --aov-specular %s (default, or BOUNCES[,MAX_ROUGHNESS]: 0..16, finite and >= 0)\n",
+                x.c_str());
+        return 2;
+      }
+      g_spec_on = true;
     } else if (a == "--denoise") {  // write the à-trous-filtered image
       const std::string x = need("--denoise");
       if (!parse_denoise(x, &dn) || !denoise_in_range(dn)) {
@@ -838,6 +910,10 @@ int main(int argc, char** argv) {
   }
   if (!aov_prefix.empty() && (orbit_n > 0 || st.samples < 1)) {
     fprintf(stderr, "--aov needs --samples >= 1 and one view (not with --orbit)\n");
+    return 2;
+  }
+  if (g_spec_on && aov_prefix.empty() && !denoise_on && !variance_on) {
+    fprintf(stderr, "--aov-specular picks the feature pass of --aov, --denoise or --denoise-variance: give one of them\n");
     return 2;
   }
   if (temporal_on && (orbit_n <= 0 || st.samples < 1)) {

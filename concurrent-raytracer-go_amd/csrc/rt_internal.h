@@ -594,6 +594,21 @@ struct AovParams {
 int launch_aov(const AovParams& p, void* stream);
 int preload_aov_kernels();
 
+// ---- specular-through feature buffers (rt_aov.hip; rt_context_render_aov_spec_async)
+// The first-hit pass's parameters and the chain's: a material is followed iff
+// its kind is metal, shiny or perfectmirror and DMat::roughness (the
+// constructors' Min(roughness, 1.0), scene_flat.cpp) <= max_roughness.
+struct AovSpecParams {
+  AovParams a;
+  double max_roughness;        // checked: finite, >= 0
+  int32_t max_bounces;         // checked: 0..16
+  int32_t pad;
+  float* specular;             // W*H
+  float* bounces;              // W*H
+};
+int launch_aov_spec(const AovSpecParams& p, void* stream);
+bool material_followed(const rt_material& m, double max_roughness);  // scene_flat.cpp: the same test on the host
+
 // ---- à-trous denoiser (rt_denoise.hip; rt_denoise_async)
 // Checked arguments of one call: image layout, device pointers.  The workspace
 // holds three 16-byte records per pixel (two colour buffers that ping-pong and

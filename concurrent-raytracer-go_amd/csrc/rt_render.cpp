@@ -773,6 +773,38 @@ int rt_context_render_cameras_async(rt_context* c, int32_t w, int32_t h, const r
 // rt_aov.hip's kernel over the whole frame, timed like a render (ev0 .. ev1) and
 // ordered behind the context's last launch, but with no schedule, no counts in
 // the statistics and no state of a progression touched.
+// The checks and parameters that both feature passes share (`who`: the call's
+// name for the messages; the five common outputs are the caller's to set).
+static int aov_setup(rt_context* c, int32_t w, int32_t h, const rt_settings* st, const rt_camera* camera,
+                     const char* who, AovParams* p) {
+  if (!c->have_scene) {
+    set_error("context has no scene");
+    return RT_E_INVALID;
+  }
+  if (st->samples < 1) {
+    set_error(std::string(who) + ": samples must be at least 1");
+    return RT_E_INVALID;
+  }
+  int rc = check_settings(st, w, h);
+  if (rc) return rc;
+  memset(p, 0, sizeof *p);
+  // (the caller's camera is read here and not again)
+  rc = camera_frame(camera ? *camera : c->flat.camera, st->camera, w, h, &p->cf);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const FlatScene& f = c->flat;
+  const int32_t use_bvh = f.bvh.empty() ? 0 : (bvh_has_cubes(f) ? 2 : 1);
+  p->g = Geo{c->d_spheres, c->d_tris, c->d_boxes, c->d_bvh, (int32_t)f.spheres.size(), (int32_t)f.tris.size(), use_bvh,
+             (int32_t)f.boxes.size()};
+  p->mats = c->d_mats;
+  p->seed_key = rt_rng_seed_key(st->seed);
+  p->W = w;
+  p->H = h;
+  p->spp = st->samples;
+  p->stack_depth = std::max(1, f.bvh_depth);
+  return RT_OK;
+}
+
 int rt_context_render_aov_async(rt_context* c, int32_t w, int32_t h, const rt_settings* st, const rt_camera* camera,
                                 const rt_aov_buffers* out, void* stream) {
   if (!c || !st || !out) {
@@ -783,32 +815,9 @@ int rt_context_render_aov_async(rt_context* c, int32_t w, int32_t h, const rt_se
     set_error("rt_context_render_aov_async: every buffer of out is NULL");
     return RT_E_INVALID;
   }
-  if (!c->have_scene) {
-    set_error("context has no scene");
-    return RT_E_INVALID;
-  }
-  if (st->samples < 1) {
-    set_error("rt_context_render_aov_async: samples must be at least 1");
-    return RT_E_INVALID;
-  }
-  int rc = check_settings(st, w, h);
-  if (rc) return rc;
   AovParams p;
-  memset(&p, 0, sizeof p);
-  // (the caller's camera is read here and not again)
-  rc = camera_frame(camera ? *camera : c->flat.camera, st->camera, w, h, &p.cf);
+  int rc = aov_setup(c, w, h, st, camera, "rt_context_render_aov_async", &p);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  const FlatScene& f = c->flat;
-  const int32_t use_bvh = f.bvh.empty() ? 0 : (bvh_has_cubes(f) ? 2 : 1);
-  p.g = Geo{c->d_spheres, c->d_tris, c->d_boxes, c->d_bvh, (int32_t)f.spheres.size(), (int32_t)f.tris.size(), use_bvh,
-            (int32_t)f.boxes.size()};
-  p.mats = c->d_mats;
-  p.seed_key = rt_rng_seed_key(st->seed);
-  p.W = w;
-  p.H = h;
-  p.spp = st->samples;
-  p.stack_depth = std::max(1, f.bvh_depth);
   p.albedo = out->d_albedo;
   p.normal = out->d_normal;
   p.depth = out->d_depth;
@@ -820,6 +829,66 @@ int rt_context_render_aov_async(rt_context* c, int32_t w, int32_t h, const rt_se
   HIP_TRY(hipEventRecord(c->ev0, s));
   const int e = launch_aov(p, s);
   if (e != hipSuccess) return launch_failed("feature buffers", e);
+  return leave_stream(c, s);
+}
+
+// Specular-through feature buffers (include/rt_api.h): the
+// same call around rt_aov.hip's aov_spec_kernel.
+void rt_aov_spec_default(rt_aov_spec* spec) {
+  if (!spec) return;
+  memset(spec, 0, sizeof *spec);
+  spec->max_bounces = 4;
+  spec->max_roughness = 0.1;  // a convention (what still looks like a mirror), not a measurement
+}
+
+static bool aov_spec_ok(const rt_aov_spec* sp) {
+  return sp && sp->max_bounces >= 0 && sp->max_bounces <= 16 && std::isfinite(sp->max_roughness) &&
+         sp->max_roughness >= 0;
+}
+
+int rt_aov_spec_follows(const rt_material* material, const rt_aov_spec* spec) {
+  if (!material || !aov_spec_ok(spec)) {
+    set_error("rt_aov_spec_follows: a material, max_bounces in [0, 16] and a finite max_roughness >= 0 are needed");
+    return RT_E_INVALID;
+  }
+  return material_followed(*material, spec->max_roughness) ? 1 : 0;
+}
+
+int rt_context_render_aov_spec_async(rt_context* c, int32_t w, int32_t h, const rt_settings* st,
+                                     const rt_camera* camera, const rt_aov_spec* spec, const rt_aov_spec_buffers* out,
+                                     void* stream) {
+  if (!c || !st || !out) {
+    set_error("rt_context_render_aov_spec_async: context, settings or out is NULL");
+    return RT_E_INVALID;
+  }
+  if (!aov_spec_ok(spec)) {
+    set_error("rt_context_render_aov_spec_async: spec must be given, max_bounces in [0, 16], max_roughness finite and >= 0");
+    return RT_E_INVALID;
+  }
+  if (!out->d_albedo && !out->d_normal && !out->d_depth && !out->d_coverage && !out->d_object && !out->d_specular &&
+      !out->d_bounces) {
+    set_error("rt_context_render_aov_spec_async: every buffer of out is NULL");
+    return RT_E_INVALID;
+  }
+  AovSpecParams q;
+  memset(&q, 0, sizeof q);
+  int rc = aov_setup(c, w, h, st, camera, "rt_context_render_aov_spec_async", &q.a);
+  if (rc) return rc;
+  q.a.albedo = out->d_albedo;
+  q.a.normal = out->d_normal;
+  q.a.depth = out->d_depth;
+  q.a.coverage = out->d_coverage;
+  q.a.object = out->d_object;
+  q.specular = out->d_specular;
+  q.bounces = out->d_bounces;
+  q.max_bounces = spec->max_bounces;
+  q.max_roughness = spec->max_roughness;
+  hipStream_t s = (hipStream_t)stream;
+  rc = enter_stream(c, s);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  const int e = launch_aov_spec(q, s);
+  if (e != hipSuccess) return launch_failed("specular-through feature buffers", e);
   return leave_stream(c, s);
 }
 

@@ -134,6 +134,15 @@ static DMat make_mat(const rt_material& m) {
   return d;
 }
 
+// The followed-material predicate of the specular-through feature pass
+// (rt_aov_spec_follows, include/rt_api.h) on the record the device tests:
+// make_mat's kind and clamped roughness.
+bool material_followed(const rt_material& m, double max_roughness) {
+  const DMat d = make_mat(m);
+  return (d.kind == RT_MAT_METAL || d.kind == RT_MAT_SHINY || d.kind == RT_MAT_PERFECTMIRROR) &&
+         d.roughness <= max_roughness;
+}
+
 static void push_tri(FlatScene* fs, v3 v0, v3 v1, v3 v2, int mat, int obj) {
   DTri t;
   memset(&t, 0, sizeof t);

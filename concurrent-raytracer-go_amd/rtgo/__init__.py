@@ -225,6 +225,33 @@ class AovBuffers(ctypes.Structure):
 AOV_NAMES = ["albedo", "normal", "depth", "coverage", "object"]
 
 
+class AovSpec(ctypes.Structure):
+    """rt_aov_spec: the parameters of the specular-through feature pass (default_aov_spec())."""
+
+    _fields_ = [
+        ("max_bounces", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+        ("max_roughness", ctypes.c_double),
+    ]
+
+
+class AovSpecBuffers(ctypes.Structure):
+    """rt_aov_spec_buffers: the device pointers of a specular-through feature pass (None / 0: not written)."""
+
+    _fields_ = [
+        ("d_albedo", ctypes.c_void_p),
+        ("d_normal", ctypes.c_void_p),
+        ("d_depth", ctypes.c_void_p),
+        ("d_coverage", ctypes.c_void_p),
+        ("d_object", ctypes.c_void_p),
+        ("d_specular", ctypes.c_void_p),
+        ("d_bounces", ctypes.c_void_p),
+    ]
+
+
+AOV_SPEC_NAMES = AOV_NAMES + ["specular", "bounces"]
+
+
 class Denoise(ctypes.Structure):
     """rt_denoise: the parameters of the à-trous denoiser (default_denoise())."""
 
@@ -425,6 +452,9 @@ EXPORTED_SYMBOLS = [
     "rt_stream_decode",
     "rt_soft_screen",
     "rt_context_render_aov_async",
+    "rt_aov_spec_default",
+    "rt_aov_spec_follows",
+    "rt_context_render_aov_spec_async",
     "rt_denoise_default",
     "rt_denoise_workspace_bytes",
     "rt_denoise_async",
@@ -567,6 +597,11 @@ def lib():
         "rt_soft_screen": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 7 + [sz, ctypes.POINTER(i32)]),
         "rt_context_render_aov_async": (ctypes.c_int, [vp, i32, i32, ctypes.POINTER(Settings), ctypes.POINTER(Camera),
                                                        ctypes.POINTER(AovBuffers), vp]),
+        "rt_aov_spec_default": (None, [ctypes.POINTER(AovSpec)]),
+        "rt_aov_spec_follows": (ctypes.c_int, [ctypes.POINTER(Material), ctypes.POINTER(AovSpec)]),
+        "rt_context_render_aov_spec_async": (ctypes.c_int, [vp, i32, i32, ctypes.POINTER(Settings),
+                                                            ctypes.POINTER(Camera), ctypes.POINTER(AovSpec),
+                                                            ctypes.POINTER(AovSpecBuffers), vp]),
         "rt_denoise_default": (None, [ctypes.POINTER(Denoise)]),
         "rt_denoise_workspace_bytes": (sz, [i32, i32]),
         "rt_denoise_async": (ctypes.c_int, [ctypes.POINTER(Denoise), i32, i32, ctypes.POINTER(DenoiseInputs), vp, vp,
@@ -872,7 +907,8 @@ class ParallelRenderer:
         return rgba
 
     def render_progressive(self, scene: Scene, width: int, height: int, pass_samples: int, time_budget=None,
-                           until_changed_pixels=None, on_pass=None, adaptive=None, denoise=None) -> np.ndarray:
+                           until_changed_pixels=None, on_pass=None, adaptive=None, denoise=None, guide="first",
+                           specular=None) -> np.ndarray:
         """Render the frame ``pass_samples`` samples at a time, on one device.
 
         ``self.settings.samples`` is the cap; the last pass is clipped to it.
@@ -900,6 +936,8 @@ class ParallelRenderer:
         denoised preview and the denoised last image is returned, its linear radiance in
         ``last_denoised_linear``.  ``changed_pixels`` and every stop rule still read the raw images, and
         ``last_linear`` and ``last_sample_counts`` stay those of the raw progression.
+        ``guide`` ("first" or "specular", with ``specular`` the pass's parameters; §4.16) picks the feature
+        pass as in ``render_denoised``.
         """
         t0 = time.perf_counter()
         if (len(self.devices) if self.devices else max(1, self.settings.num_devices)) > 1:
@@ -909,6 +947,9 @@ class ParallelRenderer:
             raise RenderError("render_progressive: pass_samples and settings.samples must be >= 1")
         _check(lib().rt_validate(ctypes.byref(scene.view), width, height, ctypes.byref(self.settings)))
         dn = _as_denoise(denoise) if denoise is not None else None
+        spec = _as_guide(guide, specular)
+        if spec is not None and dn is None:
+            raise RenderError('render_progressive: guide="specular" guides the denoiser and needs denoise')
         import torch
 
         dev = self.devices[0] if self.devices else 0
@@ -928,9 +969,7 @@ class ParallelRenderer:
                 feat, work, nbytes, out_lin, out_rgba = self._denoise_buffers(npix, width, height)
                 fst = Settings.from_buffer_copy(self.settings)
                 fst.samples = min(cap, int(pass_samples))
-                ctx.render_aov_async(width, height, fst,
-                                     AovBuffers(feat["albedo"].data_ptr(), feat["normal"].data_ptr(),
-                                                feat["depth"].data_ptr(), None, feat["object"].data_ptr()), stream=0)
+                self._guide_pass(ctx, width, height, fst, feat, None, spec)
             ctx.progressive_begin(width, height, self.settings)
             if adaptive is not None:
                 ctx.progressive_set_adaptive(adaptive["tolerance"], adaptive.get("patience", 1),
@@ -990,7 +1029,7 @@ class ParallelRenderer:
         return img
 
     def render_sequence(self, scene: Scene, width: int, height: int, cameras, seeds=None, temporal=None,
-                        denoise=None, variance=None) -> np.ndarray:
+                        denoise=None, variance=None, guide="first", specular=None) -> np.ndarray:
         """The scene from each of ``cameras`` (Camera structs or scene-file camera dicts; any number):
         an (n, H, W, 4) uint8 array, frame f that of ``render`` with the scene's camera replaced by
         cameras[f] and seed seeds[f] (None: the renderer's seed), byte for byte.
@@ -1016,8 +1055,14 @@ class ParallelRenderer:
         carries the luminance moments (rt_temporal_moments_async, the unfiltered accumulation and moments
         are fed back), rt_variance_async turns them into each frame's variance and frame f's returned image
         is rt_denoise_var_async of its accumulated colour.  ``last_variance`` is (n, H, W) float32,
-        ``last_denoised_linear`` (n, H, W, 3)."""
+        ``last_denoised_linear`` (n, H, W, 3).
+
+        guide ("first" or "specular", with ``specular`` the pass's parameters; §4.16; only together with
+        ``denoise`` or ``variance``): "specular" guides the SPATIAL filter (rt_denoise_async, or
+        rt_variance_async and rt_denoise_var_async) by the specular-through buffers of each frame.  The
+        accumulation keeps the first-hit buffers: reprojection needs the geometric depth and the camera."""
         t0 = time.perf_counter()
+        spec = _as_guide(guide, specular)
         tp = None if temporal is None or temporal is False else _as_temporal(temporal)
         dn = None if denoise is None or denoise is False else _as_denoise(denoise)
         vg = None if variance is None or variance is False else _as_variance(variance)
@@ -1027,6 +1072,8 @@ class ParallelRenderer:
             raise RenderError("render_sequence: variance is estimated from the accumulated frames and needs temporal")
         if vg is not None and dn is not None:
             raise RenderError("render_sequence: variance and denoise are two filters for the same frames: give one")
+        if spec is not None and dn is None and vg is None:
+            raise RenderError('render_sequence: guide="specular" guides the spatial filter and needs denoise or variance')
         if tp is not None and int(self.settings.samples) < 1:
             raise RenderError("render_sequence: temporal needs settings.samples >= 1")
         if (len(self.devices) if self.devices else max(1, self.settings.num_devices)) > 1:
@@ -1077,11 +1124,16 @@ class ParallelRenderer:
                     dlin = torch.zeros((n, npix * 3), dtype=torch.float32, device="cuda")
                     mom = torch.zeros((n, npix * 2), dtype=torch.float32, device="cuda")
                     var = torch.zeros((n, npix), dtype=torch.float32, device="cuda")
+                if spec is not None:  # the spatial filter's guide; the accumulation keeps the first hits
+                    sg = {k: torch.zeros_like(v) for k, v in feat[0].items()}
                 fst = Settings.from_buffer_copy(self.settings)
                 prev = None
                 for f in range(n):
                     ft = feat[f & 1]
                     fst.seed = int(seeds[f]) & (2 ** 64 - 1)
+                    if spec is not None:
+                        self._guide_pass(ctx, width, height, fst, sg, cams[f], spec)
+                    gd = sg if spec is not None else ft
                     ctx.render_aov_async(width, height, fst,
                                          AovBuffers(ft["albedo"].data_ptr(), ft["normal"].data_ptr(),
                                                     ft["depth"].data_ptr(), None, ft["object"].data_ptr()),
@@ -1093,12 +1145,12 @@ class ParallelRenderer:
                         temporal_moments_async(width, height, cur, prev, ft["albedo"].data_ptr(),
                                                mom[f - 1].data_ptr() if prev is not None else None, acc[f].data_ptr(),
                                                cnt[f].data_ptr(), mom[f].data_ptr(), None, tp, 0)
-                        variance_async(width, height, acc[f].data_ptr(), ft["normal"].data_ptr(),
-                                       ft["depth"].data_ptr(), ft["albedo"].data_ptr(), ft["object"].data_ptr(),
+                        variance_async(width, height, acc[f].data_ptr(), gd["normal"].data_ptr(),
+                                       gd["depth"].data_ptr(), gd["albedo"].data_ptr(), gd["object"].data_ptr(),
                                        mom[f].data_ptr(), cnt[f].data_ptr(), var[f].data_ptr(), vg[0], 0)
-                        denoise_var_async(width, height, acc[f].data_ptr(), ft["normal"].data_ptr(),
-                                          ft["depth"].data_ptr(), var[f].data_ptr(), ft["albedo"].data_ptr(),
-                                          ft["object"].data_ptr(), dlin[f].data_ptr(), rgba[f].data_ptr(), None,
+                        denoise_var_async(width, height, acc[f].data_ptr(), gd["normal"].data_ptr(),
+                                          gd["depth"].data_ptr(), var[f].data_ptr(), gd["albedo"].data_ptr(),
+                                          gd["object"].data_ptr(), dlin[f].data_ptr(), rgba[f].data_ptr(), None,
                                           work.data_ptr(), nbytes, vg[1], 0)
                     else:
                         temporal_async(width, height, cur, prev, acc[f].data_ptr(), cnt[f].data_ptr(),
@@ -1106,8 +1158,8 @@ class ParallelRenderer:
                     prev = temporal_frame(cur.frame, acc[f].data_ptr(), ft["depth"].data_ptr(),
                                           ft["object"].data_ptr(), ft["normal"].data_ptr(), cnt[f].data_ptr())
                     if dn is not None:
-                        denoise_async(width, height, acc[f].data_ptr(), ft["normal"].data_ptr(), ft["depth"].data_ptr(),
-                                      ft["albedo"].data_ptr(), ft["object"].data_ptr(), dlin[f].data_ptr(),
+                        denoise_async(width, height, acc[f].data_ptr(), gd["normal"].data_ptr(), gd["depth"].data_ptr(),
+                                      gd["albedo"].data_ptr(), gd["object"].data_ptr(), dlin[f].data_ptr(),
                                       rgba[f].data_ptr(), work.data_ptr(), nbytes, dn, 0)
             torch.cuda.synchronize()
             self.last_linear = lin.cpu().numpy().reshape(n, height, width, 3)
@@ -1130,14 +1182,20 @@ class ParallelRenderer:
         }
         return img
 
-    def render_aov(self, scene: Scene, width: int, height: int, camera=None) -> dict:
+    def render_aov(self, scene: Scene, width: int, height: int, camera=None, specular=None) -> dict:
         """The first-hit feature buffers of the frame (rt_context_render_aov_async) with the
         renderer's samples, seed and camera model, as numpy arrays: ``albedo`` and ``normal`` (H, W, 3)
         float32, ``depth`` and ``coverage`` (H, W) float32, ``object`` (H, W) int32 (-1: nothing hit; depth
         +Inf there).  camera: a Camera or a scene-file camera dict (with ``position``) in place of the
-        scene's.  Runs on the renderer's first device whatever ``num_devices`` is."""
+        scene's.  Runs on the renderer's first device whatever ``num_devices`` is.
+
+        specular ("default", a dict of AovSpec's fields or an AovSpec; None: the first-hit pass): the
+        specular-through feature buffers instead (rt_context_render_aov_spec_async), the
+        five arrays taken behind the scene's mirrors plus ``specular`` and ``bounces`` (H, W) float32."""
         if int(width) < 1 or int(height) < 1:
             raise RenderError(f"render_aov: invalid image size {width}x{height}")
+        spec = None if specular is None else _as_aov_spec(specular)
+        names = AOV_NAMES if spec is None else AOV_SPEC_NAMES
         if int(self.settings.samples) < 1:
             raise RenderError("render_aov: settings.samples must be >= 1")
         if isinstance(camera, dict) and "position" not in camera:
@@ -1161,12 +1219,28 @@ class ParallelRenderer:
         with torch.cuda.device(dev):
             bufs = {n: torch.zeros(npix * (3 if n in ("albedo", "normal") else 1),
                                    dtype=torch.int32 if n == "object" else torch.float32, device="cuda")
-                    for n in AOV_NAMES}
-            out = AovBuffers(*[bufs[n].data_ptr() for n in AOV_NAMES])
-            ctx.render_aov_async(width, height, self.settings, out, camera=camera, stream=0)
+                    for n in names}
+            if spec is None:
+                out = AovBuffers(*[bufs[n].data_ptr() for n in names])
+                ctx.render_aov_async(width, height, self.settings, out, camera=camera, stream=0)
+            else:
+                out = AovSpecBuffers(*[bufs[n].data_ptr() for n in names])
+                ctx.render_aov_spec_async(width, height, self.settings, out, spec=spec, camera=camera, stream=0)
             torch.cuda.synchronize()
             return {n: bufs[n].cpu().numpy().reshape((height, width, 3) if n in ("albedo", "normal")
-                                                     else (height, width)) for n in AOV_NAMES}
+                                                     else (height, width)) for n in names}
+
+    @staticmethod
+    def _guide_pass(ctx, width, height, settings, feat, camera=None, spec=None):
+        """The albedo, normal, depth and object a filter is guided by into the tensors of ``feat``: the
+        first-hit pass (spec None) or the specular-through pass (an AovSpec, §4.16)."""
+        ptr = [feat["albedo"].data_ptr(), feat["normal"].data_ptr(), feat["depth"].data_ptr(), None,
+               feat["object"].data_ptr()]
+        if spec is None:
+            ctx.render_aov_async(width, height, settings, AovBuffers(*ptr), camera=camera, stream=0)
+        else:
+            ctx.render_aov_spec_async(width, height, settings, AovSpecBuffers(*ptr, None, None), spec=spec,
+                                      camera=camera, stream=0)
 
     @staticmethod
     def _denoise_buffers(npix: int, width: int, height: int):
@@ -1184,7 +1258,7 @@ class ParallelRenderer:
         return feat, work, nbytes, out_lin, out_rgba
 
     def render_denoised(self, scene: Scene, width: int, height: int, params=None, camera=None,
-                        variance=None) -> np.ndarray:
+                        variance=None, guide="first", specular=None) -> np.ndarray:
         """Render, then denoise: the frame of ``render`` (the renderer's settings; camera as
         in ``render_aov``), its first-hit feature buffers with the same samples, seed and camera model, and
         rt_denoise_async over both, on the renderer's first device.  params: a Denoise, a dict of its fields
@@ -1193,7 +1267,12 @@ class ParallelRenderer:
 
         variance (True, or a dict of DenoiseVar's and Variance's fields; §4.15; instead of ``params``): the
         filter is rt_denoise_var_async, steered by rt_variance_async of the render.  A single frame has no
-        moments, so the variance is the spatial estimate; ``last_variance`` is (H, W) float32."""
+        moments, so the variance is the spatial estimate; ``last_variance`` is (H, W) float32.
+
+        guide ("first" or "specular"; §4.16): "specular" guides the filter by the specular-through albedo,
+        normal, depth and object (``specular``: the pass's parameters as in ``render_aov``), so that it
+        stops at the edges of what a mirror shows; "first" is the first-hit guide."""
+        spec = _as_guide(guide, specular)
         if int(width) < 1 or int(height) < 1:
             raise RenderError(f"render_denoised: invalid image size {width}x{height}")
         if int(self.settings.samples) < 1:
@@ -1227,10 +1306,7 @@ class ParallelRenderer:
                 ctx.render_async(width, height, self.settings, lin.data_ptr(), 0, 0)
             else:
                 ctx.render_cameras_async(width, height, self.settings, [camera], [lin.data_ptr()], stream=0)
-            ctx.render_aov_async(width, height, self.settings,
-                                 AovBuffers(feat["albedo"].data_ptr(), feat["normal"].data_ptr(),
-                                            feat["depth"].data_ptr(), None, feat["object"].data_ptr()),
-                                 camera=camera, stream=0)
+            self._guide_pass(ctx, width, height, self.settings, feat, camera, spec)
             if vg is not None:
                 nbytes = denoise_var_workspace_bytes(width, height)
                 work = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
@@ -1345,6 +1421,18 @@ class Context:
         cam = ctypes.byref(_as_camera(camera)) if camera is not None else None
         _check(lib().rt_context_render_aov_async(self._h, width, height, ctypes.byref(settings), cam, ctypes.byref(out),
                                                   ctypes.c_void_p(stream)))
+
+    def render_aov_spec_async(self, width, height, settings: Settings, out: AovSpecBuffers, spec=None, camera=None,
+                              stream: int = 0):
+        """rt_context_render_aov_spec_async: the specular-through feature buffers of the whole frame (DESIGN.md
+        §4.16) into the device buffers of ``out`` (an AovSpecBuffers; a pointer of None / 0 is not written):
+        the five of ``render_aov_async`` taken behind the scene's mirrors, and specular and bounces W*H
+        float32.  spec: an AovSpec, a dict of its fields, None or "default" (default_aov_spec()).  camera as
+        in ``render_aov_async``.  No image is rendered and no state of the context changes."""
+        sp = _as_aov_spec(spec)
+        cam = ctypes.byref(_as_camera(camera)) if camera is not None else None
+        _check(lib().rt_context_render_aov_spec_async(self._h, width, height, ctypes.byref(settings), cam,
+                                                       ctypes.byref(sp), ctypes.byref(out), ctypes.c_void_p(stream)))
 
     def progressive_begin(self, width, height, settings: Settings, rank: int = 0, world: int = 1,
                           layout: int = RT_LAYOUT_IMAGE):
@@ -1560,6 +1648,53 @@ def rgba_delta_async(d_a: int, d_b: int, npix: int, d_out: int, stream: int = 0)
     (pixels that differ) and d_out[1] (the largest byte difference); zeroes d_out first."""
     _check(lib().rt_rgba_delta_async(ctypes.c_void_p(d_a), ctypes.c_void_p(d_b), npix, ctypes.c_void_p(d_out),
                                      ctypes.c_void_p(stream)))
+
+
+def default_aov_spec(**over) -> AovSpec:
+    """rt_aov_spec_default (max_bounces 4, max_roughness 0.1), with the given fields replaced."""
+    sp = AovSpec()
+    lib().rt_aov_spec_default(ctypes.byref(sp))
+    for k, v in over.items():
+        if k not in ("max_bounces", "max_roughness"):
+            raise RenderError(f"default_aov_spec: no such field {k}")
+        setattr(sp, k, v)
+    return sp
+
+
+def _as_aov_spec(spec) -> AovSpec:
+    """None, True or "default": the defaults; an AovSpec as it is; a dict: default_aov_spec(**dict)."""
+    if spec is None or spec is True or spec == "default":
+        return default_aov_spec()
+    if isinstance(spec, AovSpec):
+        return spec
+    if isinstance(spec, dict):
+        return default_aov_spec(**spec)
+    raise RenderError('specular parameters are an AovSpec, a dict of its fields, "default" or None')
+
+
+def aov_spec_follows(material, spec=None) -> bool:
+    """rt_aov_spec_follows: whether the specular-through feature pass follows the reflection of ``material``
+    (a Material, or a scene-file material dict) under ``spec`` (as in ``_as_aov_spec``).  No device needed."""
+    if isinstance(material, dict):
+        material = Scene.from_json_text(json.dumps({
+            "camera": {"position": [0, 0, 1]}, "lights": [],
+            "objects": [{"type": "sphere", "position": [0, 0, 0], "radius": 1, "material": material}],
+        })).view.objects[0].material
+    sp = _as_aov_spec(spec)
+    rc = lib().rt_aov_spec_follows(ctypes.byref(material), ctypes.byref(sp))
+    _check(min(rc, 0))
+    return rc == 1
+
+
+def _as_guide(guide, specular):
+    """The AovSpec of a ``guide=`` / ``specular=`` pair, or None for the first-hit guide."""
+    if guide not in ("first", "specular"):
+        raise RenderError('guide is "first" or "specular"')
+    if guide == "first":
+        if specular is not None:
+            raise RenderError('specular parameters need guide="specular"')
+        return None
+    return _as_aov_spec(specular)
 
 
 def default_denoise(**over) -> Denoise:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async, rt_denoise, rt_denoise_inputs, rt_denoise_default, rt_denoise_workspace_bytes, rt_denoise_async, rt_denoise_host, rt_temporal, rt_temporal_frame, rt_temporal_default, rt_temporal_async, rt_temporal_host, rt_temporal_moments_async / _host, rt_variance, rt_variance_inputs, rt_variance_default, rt_variance_async / _host, rt_denoise_var, rt_denoise_var_default, rt_denoise_var_workspace_bytes, rt_denoise_var_async / _host); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async, rt_denoise, rt_denoise_inputs, rt_denoise_default, rt_denoise_workspace_bytes, rt_denoise_async, rt_denoise_host, rt_temporal, rt_temporal_frame, rt_temporal_default, rt_temporal_async, rt_temporal_host, rt_temporal_moments_async / _host, rt_variance, rt_variance_inputs, rt_variance_default, rt_variance_async / _host, rt_denoise_var, rt_denoise_var_default, rt_denoise_var_workspace_bytes, rt_denoise_var_async / _host, rt_aov_spec, rt_aov_spec_buffers, rt_aov_spec_default, rt_aov_spec_follows, rt_context_render_aov_spec_async); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -578,6 +578,92 @@ typedef struct {
 int rt_context_render_aov_async(rt_context* ctx, int32_t width, int32_t height, const rt_settings* settings,
                                 const rt_camera* camera /* NULL: the scene's */, const rt_aov_buffers* out,
                                 void* hip_stream);
+
+/* Specular-through feature buffers: the same buffers, taken
+ * not at the camera ray's first hit but at the first surface behind the
+ * mirrors -- each sample follows IDEAL mirror reflections from its first hit
+ * to the first surface that is not mirror-like -- plus a per-pixel specular
+ * flag and the number of reflections followed.  A filter guided by them stops
+ * at the edges of what a mirror shows, not only at the mirror's own.
+ *
+ * Parameters (rt_aov_spec; rt_aov_spec_default sets max_bounces 4 and
+ * max_roughness 0.1 -- the 0.1 is a convention, "what still looks like a
+ * mirror", not a measurement): max_bounces in [0, 16]; max_roughness finite
+ * and >= 0.  Anything else (a NaN included) is RT_E_INVALID.
+ *
+ * Followed materials.  A material is followed iff its kind is RT_MAT_METAL,
+ * RT_MAT_SHINY or RT_MAT_PERFECTMIRROR and Min(roughness, 1.0) <=
+ * max_roughness (Go's math.Min, the constructors' clamp; a NaN roughness
+ * compares false).  Glass and dielectric are never followed: their direction
+ * is a random choice.  rt_aov_spec_follows is this predicate on the host, no
+ * device needed: 1, 0, or RT_E_INVALID for a NULL or parameters out of range.
+ *
+ * The chain of sample s of pixel (x, y).  Ray 0 is the camera ray of the
+ * first-hit pass, unchanged (the same stream, the same two draws, the same
+ * frame).  Hit j is hitWorld(ray_j, 0.001, +Inf), with the same tie rule and
+ * the same HitRecord.  While hit j exists, its material is followed and
+ * j < max_bounces, ray j+1 has the origin Point_j (o + d * T, as the
+ * HitRecord has it) and the direction d_j.Reflect(Normal_j) =
+ * d - n * (2 * (d . n)), NOT normalised and without perturbation: exactly the
+ * ray the reference's Scatter makes for a metal of roughness 0.  No random
+ * number is drawn after the camera ray.
+ * Per sample: it HITS iff hit 0 exists; its TERMINAL hit is the last existing
+ * hit of the chain (the first surface that is not followed, or the last
+ * mirror when the next ray misses or the cap is reached); k is the number of
+ * reflections followed to reach the terminal hit (a reflected ray that misses
+ * does not count).
+ * Per pixel, sums over the hitting samples in ascending s, in binary64, with
+ * n = samples:
+ *   albedo    float3   (float)(sumA / n); each sample adds the per-component product, in chain
+ *                      order, of GetAlbedo() of hits 0 .. terminal
+ *   normal    float3   (float)(sumN / n), the terminal hit's Normal, not renormalised
+ *   depth     float    (float)(sumT / hits), +Inf when hits == 0; each sample adds
+ *                      T_0 + T_1 + ... + T_terminal, added in that order
+ *   coverage  float    (float)((double)hits / n): identical to the first-hit pass
+ *   object    int32    the terminal hittable index of the lowest hitting s, -1 when hits == 0
+ *   specular  float    (float)((double)m / n), m the samples whose hit 0 has a followed material
+ *   bounces   float    (float)(sumK / n)
+ * Reflection keeps the direction's length up to rounding, so every T is in the
+ * units of the first-hit depth and `depth` is a VIRTUAL z: the depth at which
+ * the reflected surface appears behind the mirror.  Its finiteness -- valid(p)
+ * to the filters -- is that of the first-hit depth.
+ * With max_bounces == 0, or in a scene where no material is followed, the
+ * first five buffers equal the first-hit pass bit for bit and bounces is 0.
+ * The same independence holds as for the first-hit pass: max_depth, the shadow
+ * and reflection switches, sky, every rt_tuning field and force_bvh change no
+ * bit.
+ * Known limit: a pixel that sees object A in a mirror and a pixel that sees A
+ * directly carry the same `object`; only the normal and the virtual depth
+ * separate them.  `bounces` is there for callers who want a stricter key.
+ *
+ * The call keeps the contract of rt_context_render_aov_async word for word:
+ * device pointers or NULL (not written), asynchronous on `hip_stream`, the
+ * WHOLE frame in image layout, camera NULL: the scene's (else copied before
+ * the call returns), no progression or work schedule disturbed, a render after
+ * the call byte for byte the render before it, nothing counted in
+ * rt_context_stats, its own HIP events for rt_context_last_kernel_seconds.
+ * RT_E_INVALID with a message, nothing enqueued and no buffer touched: what
+ * rt_context_render_aov_async refuses (with all SEVEN pointers NULL), and a
+ * NULL or out-of-range rt_aov_spec. */
+typedef struct {
+  int32_t max_bounces;   /* 0..16 reflections followed per sample */
+  int32_t _pad;
+  double max_roughness;  /* finite, >= 0 */
+} rt_aov_spec;
+typedef struct {
+  float* d_albedo;    /* W*H*3 */
+  float* d_normal;    /* W*H*3 */
+  float* d_depth;     /* W*H   */
+  float* d_coverage;  /* W*H   */
+  int32_t* d_object;  /* W*H   */
+  float* d_specular;  /* W*H   */
+  float* d_bounces;   /* W*H   */
+} rt_aov_spec_buffers;
+void rt_aov_spec_default(rt_aov_spec* spec);
+int rt_aov_spec_follows(const rt_material* material, const rt_aov_spec* spec);
+int rt_context_render_aov_spec_async(rt_context* ctx, int32_t width, int32_t height, const rt_settings* settings,
+                                     const rt_camera* camera /* NULL: the scene's */, const rt_aov_spec* spec,
+                                     const rt_aov_spec_buffers* out, void* hip_stream);
 
 /* Progressive rendering: one frame's samples rendered over
  * several calls, with the image of the samples so far after each.  A context
