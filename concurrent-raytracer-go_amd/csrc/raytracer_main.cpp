@@ -11,6 +11,7 @@
 //             [--temporal default|MAX_HISTORY[,DEPTH_TOL[,NORMAL_MIN]]]
 //             [--denoise-variance default|LEVELS[,SIGMA_LUM[,SIGMA_DEPTH[,NORMAL_POWER]]]]
 //             [--aov-specular default|BOUNCES[,MAX_ROUGHNESS]]
+//             [--move K:DX,DY,DZ]...
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -90,6 +91,16 @@
 // the specular-through albedo, normal, depth and object; with --orbit
 // --temporal the accumulation keeps the first-hit buffers (reprojection needs
 // the geometric depth) and only the spatial filter changes its guide.
+// --move K:DX,DY,DZ (repeatable, one per object; only with
+// --orbit) makes the sequence an animation: at view f object K (its index in
+// the scene file) stands at its position + f * (DX, DY, DZ).  The views then
+// render one by one, each after rt_context_set_scene of its own scene, and the
+// feature passes use the same scene.  With --temporal the accumulation is
+// rt_temporal_motion_async, whose table is rt_scene_motion of the scenes of
+// views f - 1 and f, so that a moving object keeps its history; --denoise,
+// --denoise-variance and --aov-specular combine with it as above.  A K outside
+// the scene, a K given twice and malformed or non-finite fields are refused
+// before anything renders.
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
@@ -346,6 +357,10 @@ static int render_progressive(const rt_scene* scene, int32_t w, int32_t h, const
 // rt_denoise_async first when dn is given.  vs (--denoise-variance, §4.15): the
 // accumulation is rt_temporal_moments_async's, the moments ping-pong with it,
 // and the image saved is rt_denoise_var_async's, steered by rt_variance_async.
+// move (--move, §4.17; num_objects * 3 doubles, or null): view f renders the scene with object k at
+// position + f * move[k], one rt_context_set_scene and one one-camera launch per view; the feature passes use
+// the same scene, and the accumulation is rt_temporal_motion_async with rt_scene_motion(view f - 1's scene,
+// view f's) as its table, so that a moving object keeps its history.
 struct VarianceSpec {
   rt_denoise_var dv;
   rt_variance vr;
@@ -368,7 +383,7 @@ static int guide_pass(rt_context* ctx, int32_t w, int32_t h, const rt_settings* 
 template <class Save>
 static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int n, double degrees,
                         Save save, rt_stats* stats, const rt_temporal* tp = nullptr, const rt_denoise* dn = nullptr,
-                        const VarianceSpec* vs = nullptr) {
+                        const VarianceSpec* vs = nullptr, const double* move = nullptr) {
   std::vector<rt_camera> cams((size_t)n);
   int rc = rt_camera_orbit(&scene->camera, n, degrees, cams.data());
   if (rc != RT_OK) return rc;
@@ -386,8 +401,31 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
     rc = RT_E_DEVICE;
     return false;
   };
-  const int per = std::min(n, RT_MAX_FRAMES);
+  const int per = move ? 1 : std::min(n, RT_MAX_FRAMES);
   std::vector<uint8_t> rgba((size_t)per * npix * 4);
+  // --move: view f's objects, and with --temporal every view's motion table on the device (view 0: zeros)
+  const size_t nobj = (size_t)std::max(scene->num_objects, 0);
+  std::vector<rt_object> moved[2];
+  rt_scene moved_scene[2] = {*scene, *scene};
+  auto move_to = [&](int f) {
+    std::vector<rt_object>& o = moved[f & 1];
+    o.assign(scene->objects, scene->objects + nobj);
+    for (size_t k = 0; k < nobj; ++k)
+      for (int j = 0; j < 3; ++j) o[k].position[j] = o[k].position[j] + (double)f * move[k * 3 + j];
+    moved_scene[f & 1].objects = o.data();
+  };
+  double* d_motion = nullptr;
+  if (rc == RT_OK && move && tp) {
+    std::vector<double> tables((size_t)n * nobj * 3, 0.0);
+    move_to(0);
+    for (int f = 1; rc == RT_OK && f < n; ++f) {
+      move_to(f);
+      if (rt_scene_motion(&moved_scene[(f - 1) & 1], &moved_scene[f & 1], tables.data() + (size_t)f * nobj * 3, nobj * 3) < 0)
+        rc = RT_E_INVALID;
+    }
+    if (rc == RT_OK && hip_ok(hipMalloc((void**)&d_motion, tables.size() * sizeof(double)), "hipMalloc"))
+      hip_ok(hipMemcpy(d_motion, tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+  }
   float* d_lin = nullptr;
   uint8_t* d_img = nullptr;
   if (rc == RT_OK && hip_ok(hipMalloc((void**)&d_lin, (size_t)per * npix * 12), "hipMalloc"))
@@ -417,6 +455,11 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
       lin[f] = d_lin + (size_t)f * npix * 3;
       img[f] = d_img + (size_t)f * npix * 4;
     }
+    if (move) {  // (per is 1: this view's scene, for its render and its feature passes)
+      move_to(f0);
+      rc = rt_context_set_scene(ctx, &moved_scene[f0 & 1], 0);
+      if (rc != RT_OK) break;
+    }
     rc = rt_context_render_cameras_async(ctx, w, h, &st, m, cams.data() + f0, tp ? seeds.data() + f0 : nullptr, 0, 1,
                                          RT_LAYOUT_IMAGE, lin, img, nullptr);
     if (rc != RT_OK) break;
@@ -442,11 +485,16 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
         g_albedo = d_sg, g_normal = d_sg + npix * 3, g_depth = d_sg + npix * 6;
         g_object = (const int32_t*)(d_sg + npix * 7);
       }
+      const rt_motion table = {d_motion ? d_motion + (size_t)(f0 + f) * nobj * 3 : nullptr, (int32_t)nobj, 0};
       if (rc == RT_OK && !vs)
-        rc = rt_temporal_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, acc, cnt, img[f], nullptr);
+        rc = move ? rt_temporal_motion_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, &table, nullptr, nullptr,
+                                             acc, cnt, nullptr, img[f], nullptr)
+                  : rt_temporal_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, acc, cnt, img[f], nullptr);
       if (rc == RT_OK && vs) {
-        rc = rt_temporal_moments_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, albedo, prev_moments, acc, cnt,
-                                       mom, nullptr, nullptr);
+        rc = move ? rt_temporal_motion_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, &table, albedo,
+                                             prev_moments, acc, cnt, mom, nullptr, nullptr)
+                  : rt_temporal_moments_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, albedo, prev_moments,
+                                              acc, cnt, mom, nullptr, nullptr);
         prev_moments = mom;
         const rt_variance_inputs vin = {acc, g_normal, g_depth, g_albedo, g_object, mom, cnt};
         if (rc == RT_OK) rc = rt_variance_async(&vs->vr, w, h, &vin, var, nullptr);
@@ -471,7 +519,7 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
   }
   const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - save_s;
-  for (void* p : {(void*)d_lin, (void*)d_img, (void*)d_tp, (void*)d_sg, d_work})
+  for (void* p : {(void*)d_lin, (void*)d_img, (void*)d_tp, (void*)d_sg, (void*)d_motion, d_work})
     if (p) (void)hipFree(p);
   rt_context_destroy(ctx);
   if (rc != RT_OK) {
@@ -708,8 +756,32 @@ static bool parse_temporal(const std::string& x, rt_temporal* tp) {
          tp->normal_min >= -1 && tp->normal_min <= 1;
 }
 
+// --move SPEC: K:DX,DY,DZ -- an object index and three finite doubles
+static bool parse_move(const std::string& x, long long* k, double v[3]) {
+  const size_t colon = x.find(':');
+  if (colon == std::string::npos || colon == 0) return false;
+  if (!parse_int(x.substr(0, colon).c_str(), k) || *k < 0) return false;
+  size_t pos = colon + 1;
+  for (int nf = 0; nf < 3; ++nf) {
+    const size_t c = x.find(',', pos);
+    if ((c == std::string::npos) != (nf == 2)) return false;  // exactly three fields
+    const std::string part = x.substr(pos, c == std::string::npos ? std::string::npos : c - pos);
+    char* end = nullptr;
+    errno = 0;
+    v[nf] = strtod(part.c_str(), &end);
+    if (part.empty() || !end || *end || errno != 0 || !std::isfinite(v[nf])) return false;
+    pos = c + 1;
+  }
+  return true;
+}
+
 int main(int argc, char** argv) {
   std::vector<std::string> args;
+  struct Move {
+    long long k;
+    double v[3];
+  };
+  std::vector<Move> moves;     // --move K:DX,DY,DZ, repeatable
   bool temporal_on = false;    // --temporal SPEC
   rt_temporal tpar;
   rt_temporal_default(&tpar);
@@ -881,6 +953,19 @@ int main(int argc, char** argv) {
         return 2;
       }
       temporal_on = true;
+    } else if (a == "--move") {  // --orbit: object K is offset by f * (DX, DY, DZ) at view f
+      const std::string x = need("--move");
+      Move mv;
+      if (!parse_move(x, &mv.k, mv.v)) {
+        fprintf(stderr, "invalid --move %s (K:DX,DY,DZ: an object index >= 0 and three finite numbers)\n", x.c_str());
+        return 2;
+      }
+      for (const Move& o : moves)
+        if (o.k == mv.k) {
+          fprintf(stderr, "invalid --move %s (object %lld is given twice)\n", x.c_str(), mv.k);
+          return 2;
+        }
+      moves.push_back(mv);
     } else if (a == "--sky") {  // opt-in sky on miss (atmosphere.go presets); default: black
       const std::string k = need("--sky");
       if (k == "none") st.sky = RT_SKY_NONE;
@@ -918,6 +1003,10 @@ int main(int argc, char** argv) {
   }
   if (temporal_on && (orbit_n <= 0 || st.samples < 1)) {
     fprintf(stderr, "--temporal accumulates the views of --orbit and needs --samples >= 1\n");
+    return 2;
+  }
+  if (!moves.empty() && orbit_n <= 0) {
+    fprintf(stderr, "--move moves objects from view to view and needs --orbit\n");
     return 2;
   }
   if (denoise_on && ((orbit_n > 0 && !temporal_on) || st.samples < 1)) {
@@ -975,6 +1064,19 @@ int main(int argc, char** argv) {
   if (rt_scene_load_json(scene_file.c_str(), 0, &sb) != RT_OK) {
     printf("Error loading scene: %s\n", rt_last_error());
     return 1;
+  }
+  std::vector<double> move_table;  // --move: num_objects * 3, each object's offset per view
+  if (!moves.empty()) {
+    const long long nobj = rt_scene_view(sb)->num_objects;
+    move_table.assign((size_t)std::max(nobj, 0LL) * 3, 0.0);
+    for (const Move& mv : moves) {
+      if (mv.k >= nobj) {
+        fprintf(stderr, "invalid --move %lld:...: the scene has %lld objects\n", mv.k, nobj);
+        rt_scene_free(sb);
+        return 2;
+      }
+      for (int j = 0; j < 3; ++j) move_table[(size_t)mv.k * 3 + j] = mv.v[j];
+    }
   }
   const long long aw = llabs(w), ah = llabs(h);
   if ((w <= 0 || h <= 0) && aw <= 65536 && ah <= 65536) {
@@ -1062,7 +1164,7 @@ int main(int argc, char** argv) {
     if (rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK ||
         render_orbit(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)orbit_n, orbit_deg, save, &stats,
                      temporal_on ? &tpar : nullptr, denoise_on && !variance_on ? &dn : nullptr,
-                     variance_on ? &vspec : nullptr) != RT_OK) {
+                     variance_on ? &vspec : nullptr, moves.empty() ? nullptr : move_table.data()) != RT_OK) {
       if (!save_failed) fprintf(stderr, "render failed: %s\n", rt_last_error());
       rt_scene_free(sb);
       return save_failed ? 1 : 2;

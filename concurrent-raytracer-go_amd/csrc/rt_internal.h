@@ -679,6 +679,15 @@ int launch_variance(const VarianceParams& p, void* stream);
 int launch_denoise_var(const DenoiseVarParams& p, void* stream);
 int preload_variance_kernels();
 
+// ---- temporal accumulation with per-object motion (rt_motion.hip; rt_temporal_motion_async)
+struct TemporalMotionParams {
+  TemporalMomentsParams m;     // out_moments null: the colour-only form (cur_albedo and prev_moments null too)
+  const double* motion;        // num_objects * 3, a device pointer
+  int32_t num_objects;         // >= 1
+};
+int launch_temporal_motion(const TemporalMotionParams& p, void* stream);
+int preload_motion_kernels();
+
 // ---------------------------------------------------------------- wavefront path
 // (rt_wavefront.hip: BVH scenes)
 constexpr int kWfShards = 8;           // queues / path arrays are split in 8 shards (one atomic word each)

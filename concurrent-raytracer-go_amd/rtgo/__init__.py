@@ -302,6 +302,17 @@ class TemporalFrame(ctypes.Structure):
     ]
 
 
+class Motion(ctypes.Structure):
+    """rt_motion: the per-object translations of rt_temporal_motion_async: ``motion`` points
+    to num_objects rows of 3 doubles (a device pointer for the _async call)."""
+
+    _fields_ = [
+        ("motion", ctypes.c_void_p),
+        ("num_objects", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+    ]
+
+
 class Variance(ctypes.Structure):
     """rt_variance: the parameters of the variance pass (default_variance())."""
 
@@ -471,6 +482,9 @@ EXPORTED_SYMBOLS = [
     "rt_denoise_var_workspace_bytes",
     "rt_denoise_var_async",
     "rt_denoise_var_host",
+    "rt_temporal_motion_async",
+    "rt_temporal_motion_host",
+    "rt_scene_motion",
 ]
 
 _lib = None
@@ -625,6 +639,14 @@ def lib():
                                                  vp, vp, vp, vp, sz, vp]),
         "rt_denoise_var_host": (ctypes.c_int, [ctypes.POINTER(DenoiseVar), i32, i32, ctypes.POINTER(DenoiseInputs), vp,
                                                 vp, vp, vp]),
+        "rt_temporal_motion_async": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
+                                                     ctypes.POINTER(TemporalFrame), ctypes.POINTER(Motion), vp, vp, vp,
+                                                     vp, vp, vp, vp]),
+        "rt_temporal_motion_host": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
+                                                    ctypes.POINTER(TemporalFrame), ctypes.POINTER(Motion), vp, vp, vp,
+                                                    vp, vp, vp]),
+        "rt_scene_motion": (ctypes.c_int, [ctypes.POINTER(SceneView), ctypes.POINTER(SceneView),
+                                            ctypes.POINTER(ctypes.c_double), sz]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -737,6 +759,22 @@ class Scene:
     @property
     def warnings(self) -> int:
         return lib().rt_scene_warnings(self._handle) if self._handle is not None else 0
+
+    def translated(self, offsets) -> "Scene":
+        """A copy of the scene with object k moved by offsets[k] (a (num_objects, 3) array):
+        position + offset in binary64, everything else as it is."""
+        n = self.num_objects
+        off = np.asarray(offsets, np.float64)
+        if off.shape != (n, 3) or not np.isfinite(off).all():
+            raise RenderError(f"Scene.translated: offsets are a finite ({n}, 3) array, one row per object")
+        objs = []
+        for k in range(n):
+            ob = Object.from_buffer_copy(self._view.objects[k])
+            for j in range(3):
+                ob.position[j] = ob.position[j] + float(off[k, j])
+            objs.append(ob)
+        lights = [Light.from_buffer_copy(self._view.lights[k]) for k in range(self._view.num_lights)]
+        return Scene(objects=objs, lights=lights, camera=Camera.from_buffer_copy(self._view.camera))
 
     def print_hittables(self):
         if self._handle is not None:
@@ -1029,7 +1067,7 @@ class ParallelRenderer:
         return img
 
     def render_sequence(self, scene: Scene, width: int, height: int, cameras, seeds=None, temporal=None,
-                        denoise=None, variance=None, guide="first", specular=None) -> np.ndarray:
+                        denoise=None, variance=None, guide="first", specular=None, offsets=None) -> np.ndarray:
         """The scene from each of ``cameras`` (Camera structs or scene-file camera dicts; any number):
         an (n, H, W, 4) uint8 array, frame f that of ``render`` with the scene's camera replaced by
         cameras[f] and seed seeds[f] (None: the renderer's seed), byte for byte.
@@ -1060,7 +1098,15 @@ class ParallelRenderer:
         guide ("first" or "specular", with ``specular`` the pass's parameters; §4.16; only together with
         ``denoise`` or ``variance``): "specular" guides the SPATIAL filter (rt_denoise_async, or
         rt_variance_async and rt_denoise_var_async) by the specular-through buffers of each frame.  The
-        accumulation keeps the first-hit buffers: reprojection needs the geometric depth and the camera."""
+        accumulation keeps the first-hit buffers: reprojection needs the geometric depth and the camera.
+
+        offsets (an (n, num_objects, 3) array; §4.17): frame f is the scene with object k moved by
+        offsets[f][k] (Scene.translated), byte for byte ``render`` of that moved scene with cameras[f] and
+        seeds[f].  The frames then render one by one, each after rt_context_set_scene of its own scene, and
+        the feature passes use the same scene.  With ``temporal`` the accumulation is
+        rt_temporal_motion_async with scene_motion(frame f - 1's scene, frame f's) as its table, so that a
+        moving object keeps its history; ``denoise``, ``variance`` and ``guide`` compose as above.  Without
+        ``offsets`` the method and its launches are what they were."""
         t0 = time.perf_counter()
         spec = _as_guide(guide, specular)
         tp = None if temporal is None or temporal is False else _as_temporal(temporal)
@@ -1086,7 +1132,19 @@ class ParallelRenderer:
             raise RenderError(f"render_sequence: {len(seeds)} seeds for {n} cameras")
         if seeds is None and tp is not None:
             seeds = [(int(self.settings.seed) + f) & (2 ** 64 - 1) for f in range(n)]
-        _check(lib().rt_validate(ctypes.byref(scene.view), width, height, ctypes.byref(self.settings)))
+        scenes = None
+        if offsets is not None:
+            off = np.asarray(offsets, np.float64)
+            if off.shape != (n, scene.num_objects, 3):
+                raise RenderError(f"render_sequence: offsets have shape {off.shape}, expected "
+                                  f"({n}, {scene.num_objects}, 3): one row per frame and object")
+            scenes = [scene.translated(off[f]) for f in range(n)]
+            tables = [np.zeros((max(1, scene.num_objects), 3), np.float64)]  # (frame 0 starts the history)
+            tables += [scene_motion(scenes[f - 1], scenes[f]) for f in range(1, n)]
+            if tp is not None and scene.num_objects < 1:
+                raise RenderError("render_sequence: offsets with temporal need a scene with objects")
+        for s in (scenes if scenes is not None else [scene]):
+            _check(lib().rt_validate(ctypes.byref(s.view), width, height, ctypes.byref(self.settings)))
         import torch
 
         dev = self.devices[0] if self.devices else 0
@@ -1095,12 +1153,18 @@ class ParallelRenderer:
         ctx = self._prog_ctx
         if self._tuning is not None:
             ctx.set_tuning(self._tuning)
-        ctx.set_scene(scene)
+        if scenes is None:
+            ctx.set_scene(scene)
         npix = width * height
         with torch.cuda.device(dev):
             lin = torch.zeros((n, npix * 3), dtype=torch.float32, device="cuda")
             rgba = torch.zeros((n, npix * 4), dtype=torch.uint8, device="cuda")
-            for f0 in range(0, n, RT_MAX_FRAMES):
+            for f in range(n) if scenes is not None else ():  # moved frames: one scene and one launch each
+                ctx.set_scene(scenes[f])
+                ctx.render_cameras_async(width, height, self.settings, [cams[f]], [lin[f].data_ptr()],
+                                         [rgba[f].data_ptr()], seeds=None if seeds is None else [int(seeds[f])],
+                                         stream=0)
+            for f0 in range(0, n, RT_MAX_FRAMES) if scenes is None else ():
                 f1 = min(n, f0 + RT_MAX_FRAMES)
                 ctx.render_cameras_async(width, height, self.settings, cams[f0:f1],
                                          [lin[f].data_ptr() for f in range(f0, f1)],
@@ -1128,9 +1192,13 @@ class ParallelRenderer:
                     sg = {k: torch.zeros_like(v) for k, v in feat[0].items()}
                 fst = Settings.from_buffer_copy(self.settings)
                 prev = None
+                if scenes is not None:
+                    mot = [torch.from_numpy(t).to("cuda") for t in tables]
                 for f in range(n):
                     ft = feat[f & 1]
                     fst.seed = int(seeds[f]) & (2 ** 64 - 1)
+                    if scenes is not None:
+                        ctx.set_scene(scenes[f])
                     if spec is not None:
                         self._guide_pass(ctx, width, height, fst, sg, cams[f], spec)
                     gd = sg if spec is not None else ft
@@ -1142,9 +1210,16 @@ class ParallelRenderer:
                                          lin[f].data_ptr(), ft["depth"].data_ptr(), ft["object"].data_ptr(),
                                          ft["normal"].data_ptr())
                     if vg is not None:
-                        temporal_moments_async(width, height, cur, prev, ft["albedo"].data_ptr(),
-                                               mom[f - 1].data_ptr() if prev is not None else None, acc[f].data_ptr(),
-                                               cnt[f].data_ptr(), mom[f].data_ptr(), None, tp, 0)
+                        if scenes is not None:
+                            temporal_motion_async(width, height, cur, prev, mot[f].data_ptr(), mot[f].shape[0],
+                                                  acc[f].data_ptr(), cnt[f].data_ptr(), None, tp, 0,
+                                                  d_cur_albedo=ft["albedo"].data_ptr(),
+                                                  d_prev_moments=mom[f - 1].data_ptr() if prev is not None else None,
+                                                  d_out_moments=mom[f].data_ptr())
+                        else:
+                            temporal_moments_async(width, height, cur, prev, ft["albedo"].data_ptr(),
+                                                   mom[f - 1].data_ptr() if prev is not None else None,
+                                                   acc[f].data_ptr(), cnt[f].data_ptr(), mom[f].data_ptr(), None, tp, 0)
                         variance_async(width, height, acc[f].data_ptr(), gd["normal"].data_ptr(),
                                        gd["depth"].data_ptr(), gd["albedo"].data_ptr(), gd["object"].data_ptr(),
                                        mom[f].data_ptr(), cnt[f].data_ptr(), var[f].data_ptr(), vg[0], 0)
@@ -1152,6 +1227,9 @@ class ParallelRenderer:
                                           gd["depth"].data_ptr(), var[f].data_ptr(), gd["albedo"].data_ptr(),
                                           gd["object"].data_ptr(), dlin[f].data_ptr(), rgba[f].data_ptr(), None,
                                           work.data_ptr(), nbytes, vg[1], 0)
+                    elif scenes is not None:
+                        temporal_motion_async(width, height, cur, prev, mot[f].data_ptr(), mot[f].shape[0],
+                                              acc[f].data_ptr(), cnt[f].data_ptr(), rgba[f].data_ptr(), tp, 0)
                     else:
                         temporal_async(width, height, cur, prev, acc[f].data_ptr(), cnt[f].data_ptr(),
                                        rgba[f].data_ptr(), tp, 0)
@@ -1959,6 +2037,73 @@ def temporal_moments_host(cur: dict, prev=None, params=None):
                                           ctypes.byref(fp) if fp is not None else None, ac["albedo"], ap["moments"],
                                           out.ctypes.data, cnt.ctypes.data, mom.ctypes.data, rgba.ctypes.data))
     return out, cnt, mom, rgba
+
+
+def scene_motion(prev: "Scene", cur: "Scene") -> np.ndarray:
+    """rt_scene_motion: the (num_objects, 3) float64 table of each object's translation from
+    ``prev`` to ``cur``.  Refused when the scenes differ in anything but their objects' positions (lights and
+    cameras are not compared) or a position is not finite."""
+    n = max(0, int(cur.num_objects))
+    out = np.zeros((n, 3), np.float64)
+    rc = lib().rt_scene_motion(ctypes.byref(prev.view), ctypes.byref(cur.view),
+                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out.size)
+    if rc < 0:
+        _check(rc)
+    return out
+
+
+def temporal_motion_async(width: int, height: int, cur: TemporalFrame, prev, d_motion: int, num_objects: int,
+                          d_out_color: int, d_out_count: int, d_out_rgba=None, params=None, stream: int = 0,
+                          d_cur_albedo=None, d_prev_moments=None, d_out_moments=None):
+    """rt_temporal_motion_async: temporal_async (with d_out_moments: temporal_moments_async)
+    for objects that moved.  d_motion is a device pointer to num_objects rows of 3 doubles, row k the
+    translation of object k from the previous frame to the current one; both frames must carry ``object``."""
+    p = _as_temporal(params)
+    m = Motion(d_motion, num_objects, 0)
+    _check(lib().rt_temporal_motion_async(ctypes.byref(p), width, height, ctypes.byref(cur),
+                                          ctypes.byref(prev) if prev is not None else None, ctypes.byref(m),
+                                          ctypes.c_void_p(d_cur_albedo), ctypes.c_void_p(d_prev_moments),
+                                          ctypes.c_void_p(d_out_color), ctypes.c_void_p(d_out_count),
+                                          ctypes.c_void_p(d_out_moments), ctypes.c_void_p(d_out_rgba),
+                                          ctypes.c_void_p(stream)))
+
+
+def temporal_motion_host(cur: dict, prev=None, motion=None, params=None, moments: bool = False):
+    """rt_temporal_motion_host: temporal_host (moments=True: temporal_moments_host, with ``albedo`` in cur and
+    ``moments`` in prev) with ``motion``, an (num_objects, 3) float64 table.  Returns (color, count, rgba),
+    or (color, count, moments, rgba)."""
+    what = "temporal_motion_host"
+    color = np.ascontiguousarray(cur["color"], np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise RenderError(f"{what}: color is an (H, W, 3) array")
+    table = np.ascontiguousarray(motion, np.float64) if motion is not None else None
+    if table is None or table.ndim != 2 or table.shape[1] != 3:
+        raise RenderError(f"{what}: motion is a (num_objects, 3) array")
+    h, w = color.shape[:2]
+    keep = []
+
+    def frame_of(d, name):
+        a = _host_arrays(f"{what}: {name}", h, w, keep,
+                         color=(d.get("color"), np.float32, (h, w, 3)), depth=(d.get("depth"), np.float32, (h, w)),
+                         object=(d.get("object"), np.int32, (h, w)), normal=(d.get("normal"), np.float32, (h, w, 3)),
+                         count=(d.get("count"), np.float32, (h, w)), albedo=(d.get("albedo"), np.float32, (h, w, 3)),
+                         moments=(d.get("moments"), np.float32, (h, w, 2)))
+        return temporal_frame(d["frame"], a["color"], a["depth"], a["object"], a["normal"], a["count"]), a
+
+    fc, ac = frame_of(cur, "cur")
+    fp, ap = frame_of(prev, "prev") if prev is not None else (None, {"moments": None})
+    p = _as_temporal(params)
+    m = Motion(table.ctypes.data, table.shape[0], 0)
+    out = np.zeros((h, w, 3), np.float32)
+    cnt = np.zeros((h, w), np.float32)
+    mom = np.zeros((h, w, 2), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    _check(lib().rt_temporal_motion_host(ctypes.byref(p), w, h, ctypes.byref(fc),
+                                         ctypes.byref(fp) if fp is not None else None, ctypes.byref(m),
+                                         ac["albedo"] if moments else None, ap["moments"] if moments else None,
+                                         out.ctypes.data, cnt.ctypes.data, mom.ctypes.data if moments else None,
+                                         rgba.ctypes.data))
+    return (out, cnt, mom, rgba) if moments else (out, cnt, rgba)
 
 
 def variance_async(width: int, height: int, d_color: int, d_normal: int, d_depth: int, d_albedo=None, d_object=None,

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async, rt_denoise, rt_denoise_inputs, rt_denoise_default, rt_denoise_workspace_bytes, rt_denoise_async, rt_denoise_host, rt_temporal, rt_temporal_frame, rt_temporal_default, rt_temporal_async, rt_temporal_host, rt_temporal_moments_async / _host, rt_variance, rt_variance_inputs, rt_variance_default, rt_variance_async / _host, rt_denoise_var, rt_denoise_var_default, rt_denoise_var_workspace_bytes, rt_denoise_var_async / _host, rt_aov_spec, rt_aov_spec_buffers, rt_aov_spec_default, rt_aov_spec_follows, rt_context_render_aov_spec_async); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
+#define RT_ABI_VERSION 8  /* 8: rt_settings.camera (was _pad2), rt_camera_frame (also added at 8, additive only: rt_adaptive, rt_context_progressive_set_adaptive / _counts_async / _state, rt_adaptive_step, rt_scene_cone_rows, rt_context_render_cameras_async, rt_camera_orbit, rt_stream_decode, rt_aov_buffers, rt_context_render_aov_async, rt_denoise, rt_denoise_inputs, rt_denoise_default, rt_denoise_workspace_bytes, rt_denoise_async, rt_denoise_host, rt_temporal, rt_temporal_frame, rt_temporal_default, rt_temporal_async, rt_temporal_host, rt_temporal_moments_async / _host, rt_variance, rt_variance_inputs, rt_variance_default, rt_variance_async / _host, rt_denoise_var, rt_denoise_var_default, rt_denoise_var_workspace_bytes, rt_denoise_var_async / _host, rt_aov_spec, rt_aov_spec_buffers, rt_aov_spec_default, rt_aov_spec_follows, rt_context_render_aov_spec_async, rt_motion, rt_temporal_motion_async / _host, rt_scene_motion); 7: rt_context_progressive_*, rt_rgba_delta_async; 6: rt_tuning stream* fields, rt_context_stats stream_*; 5: rt_tuning tail_* fields; 4: rt_renderer_rank_seconds takes a capacity */
 
 /* status codes */
 #define RT_OK 0
@@ -1078,6 +1078,78 @@ int rt_denoise_var_async(const rt_denoise_var* params, int32_t width, int32_t he
                          void* hip_stream);
 int rt_denoise_var_host(const rt_denoise_var* params, int32_t width, int32_t height, const rt_denoise_inputs* in,
                         const float* variance, float* out_linear, uint8_t* out_rgba, float* out_variance);
+
+/* Temporal accumulation with per-object motion: the
+ * accumulation above for scenes whose objects move between the frames of a
+ * sequence.  rt_temporal_async assumes that nothing but the camera moved, so
+ * an object that moves loses its history, and where it overlaps its old place
+ * it blends in another surface point.  Here every hittable has a translation
+ * from the previous frame to the current one, and a pixel's world point is
+ * moved back by its object's before it is taken into the previous camera.
+ *
+ * The table (rt_motion): `motion` holds num_objects rows of 3 doubles, row k
+ * the translation of hittable k from the previous frame to the current one
+ * (position in cur minus position in prev).  Hittable k is the rt_object index
+ * that the `object` buffers hold (rt_aov_buffers.d_object).  rt_scene_motion
+ * makes the table from two scenes.
+ *
+ * Per pixel, every step is rt_temporal_async's, and rt_temporal_moments_async's
+ * when out_moments is given, bit for bit and in their order.  The one addition
+ * is in step 3: after P = o + dir * z, let id = cur.object[p];
+ * m = motion[id] when 0 <= id < num_objects, else m = (0, 0, 0);
+ * Pm = P - m and d = Pm - o', per component.  t, fx, fy and the depth test of
+ * steps 4 and 5 then refer to where that surface point WAS.  The id test and
+ * the normal test are unchanged: a translation keeps both.
+ *   - With a table of zeros every output equals the existing calls' bit for
+ *     bit, for every input: x - 0.0 is x, signed zeros and NaNs included.
+ *   - id is compared against the table's bounds before it forms an address;
+ *     that guarded address is the only one that comes from a pixel's value.
+ *   - Non-finite table entries cannot fault and carry no contract.
+ *
+ * Moments.  Without out_moments, cur_albedo and prev_moments must be NULL and
+ * the call is the colour-only form (rt_temporal_async's outputs).  With it,
+ * rt_temporal_moments_async's rules apply (cur_albedo optional, prev_moments
+ * exactly when prev is given, out_moments != prev_moments).
+ *
+ * rt_temporal_motion_async: every buffer pointer, the table included, is a
+ * DEVICE pointer of the current device; the rt_motion struct itself is read on
+ * the host before the call returns.  No workspace, no context, no allocation;
+ * asynchronous on `hip_stream`.  RT_E_INVALID with a message, nothing enqueued
+ * and no buffer touched: whatever rt_temporal_async (or, with out_moments,
+ * rt_temporal_moments_async) refuses; a NULL motion or a NULL table;
+ * num_objects < 1; a NULL object in either frame (the table is indexed by it,
+ * so ids are required here); cur_albedo or prev_moments without out_moments.
+ * rt_temporal_motion_host does the same with host pointers and no device.
+ *
+ * rt_scene_motion runs on the host and needs no device.  It writes
+ * out[k * 3 + j] = cur.objects[k].position[j] - prev.objects[k].position[j] and
+ * returns num_objects.  RT_E_INVALID when the scenes differ in their object
+ * count or in any object's type, size, radius or material (a rigid translation
+ * is the only motion this models), when a position is not finite, or when
+ * capacity (in doubles) is below num_objects * 3.  Lights and cameras are not
+ * compared: the camera reaches the pass through the frames, and a moving light
+ * is the caller's business.
+ *
+ * Known limits.  A static pixel under a moving object's shadow keeps its old
+ * history, and what a moving mirror shows does not reproject (its lighting
+ * changes as it moves; DESIGN.md §4.17 has the figures).  max_history bounds
+ * both.  Rotations and deformations are not modelled. */
+typedef struct {
+  const double* motion;  /* num_objects * 3 */
+  int32_t num_objects;
+  int32_t _pad;
+} rt_motion;
+int rt_temporal_motion_async(const rt_temporal* params, int32_t width, int32_t height, const rt_temporal_frame* cur,
+                             const rt_temporal_frame* prev /* NULL: start a history */,
+                             const rt_motion* motion /* device table */, const float* d_cur_albedo,
+                             const float* d_prev_moments, float* d_out_color, float* d_out_count,
+                             float* d_out_moments /* may be NULL */, uint8_t* d_out_rgba /* may be NULL */,
+                             void* hip_stream);
+int rt_temporal_motion_host(const rt_temporal* params, int32_t width, int32_t height, const rt_temporal_frame* cur,
+                            const rt_temporal_frame* prev, const rt_motion* motion, const float* cur_albedo,
+                            const float* prev_moments, float* out_color, float* out_count, float* out_moments,
+                            uint8_t* out_rgba);
+int rt_scene_motion(const rt_scene* prev, const rt_scene* cur, double* out, size_t capacity);
 
 /* What a context has done so far (diagnostics): work schedules built (a new
  * scene, frame, rank or settings key; a measured re-cut counts too),
