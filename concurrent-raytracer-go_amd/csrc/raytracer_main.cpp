@@ -12,6 +12,7 @@
 //             [--denoise-variance default|LEVELS[,SIGMA_LUM[,SIGMA_DEPTH[,NORMAL_POWER]]]]
 //             [--aov-specular default|BOUNCES[,MAX_ROUGHNESS]]
 //             [--move K:DX,DY,DZ]...
+//             [--clip default|RADIUS[,GAMMA[,MIN_TAPS[,MIN_HALF]]]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -101,6 +102,13 @@
 // --denoise-variance and --aov-specular combine with it as above.  A K outside
 // the scene, a K given twice and malformed or non-finite fields are refused
 // before anything renders.
+// --clip SPEC (only with --orbit N --temporal ...) rectifies
+// the history: the accumulation is rt_temporal_clip_async, which clips each
+// pixel's reprojected history to mean +- GAMMA sigma of the current view's
+// demodulated colour in a (2 RADIUS + 1)^2 window (the view's albedo
+// demodulates it).  SPEC is `default` (rt_history_clip_default) or up to four
+// comma-separated fields that replace the defaults from the left.  It combines
+// with --move, --denoise, --denoise-variance and --aov-specular as above.
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
@@ -383,7 +391,8 @@ static int guide_pass(rt_context* ctx, int32_t w, int32_t h, const rt_settings* 
 template <class Save>
 static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int n, double degrees,
                         Save save, rt_stats* stats, const rt_temporal* tp = nullptr, const rt_denoise* dn = nullptr,
-                        const VarianceSpec* vs = nullptr, const double* move = nullptr) {
+                        const VarianceSpec* vs = nullptr, const double* move = nullptr,
+                        const rt_history_clip* hc = nullptr) {
   std::vector<rt_camera> cams((size_t)n);
   int rc = rt_camera_orbit(&scene->camera, n, degrees, cams.data());
   if (rc != RT_OK) return rc;
@@ -486,15 +495,20 @@ static int render_orbit(const rt_scene* scene, int32_t w, int32_t h, const rt_se
         g_object = (const int32_t*)(d_sg + npix * 7);
       }
       const rt_motion table = {d_motion ? d_motion + (size_t)(f0 + f) * nobj * 3 : nullptr, (int32_t)nobj, 0};
-      if (rc == RT_OK && !vs)
+      if (rc == RT_OK && hc)  // --clip: the same outputs as the calls below, the history rectified (§4.18)
+        rc = rt_temporal_clip_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, move ? &table : nullptr, hc, albedo,
+                                    vs ? prev_moments : nullptr, acc, cnt, vs ? mom : nullptr, nullptr,
+                                    vs ? nullptr : img[f], nullptr);
+      if (rc == RT_OK && !vs && !hc)
         rc = move ? rt_temporal_motion_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, &table, nullptr, nullptr,
                                              acc, cnt, nullptr, img[f], nullptr)
                   : rt_temporal_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, acc, cnt, img[f], nullptr);
       if (rc == RT_OK && vs) {
-        rc = move ? rt_temporal_motion_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, &table, albedo,
-                                             prev_moments, acc, cnt, mom, nullptr, nullptr)
-                  : rt_temporal_moments_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, albedo, prev_moments,
-                                              acc, cnt, mom, nullptr, nullptr);
+        if (!hc)
+          rc = move ? rt_temporal_motion_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, &table, albedo,
+                                               prev_moments, acc, cnt, mom, nullptr, nullptr)
+                    : rt_temporal_moments_async(tp, w, h, &cur, f0 + f > 0 ? &prev_frame : nullptr, albedo,
+                                                prev_moments, acc, cnt, mom, nullptr, nullptr);
         prev_moments = mom;
         const rt_variance_inputs vin = {acc, g_normal, g_depth, g_albedo, g_object, mom, cnt};
         if (rc == RT_OK) rc = rt_variance_async(&vs->vr, w, h, &vin, var, nullptr);
@@ -756,6 +770,35 @@ static bool parse_temporal(const std::string& x, rt_temporal* tp) {
          tp->normal_min >= -1 && tp->normal_min <= 1;
 }
 
+// --clip SPEC: `default`, or RADIUS[,GAMMA[,MIN_TAPS[,MIN_HALF]]] over the defaults within rt_history_clip's
+// ranges (include/rt_api.h), checked before anything is rendered
+static bool parse_clip(const std::string& x, rt_history_clip* hc) {
+  rt_history_clip_default(hc);
+  if (x == "default") return true;
+  if (x.empty()) return false;
+  size_t pos = 0;
+  for (int nf = 0;; ++nf) {
+    if (nf == 4) return false;  // a fifth field
+    const size_t c = x.find(',', pos);
+    const std::string part = x.substr(pos, c == std::string::npos ? std::string::npos : c - pos);
+    if (nf == 0 || nf == 2) {
+      long long v = 0;
+      if (!parse_int(part.c_str(), &v) || v < -1 || v > 1000000) return false;
+      (nf == 0 ? hc->radius : hc->min_taps) = (int32_t)v;
+    } else {
+      char* end = nullptr;
+      errno = 0;
+      const double f = strtod(part.c_str(), &end);
+      if (part.empty() || !end || *end || errno != 0) return false;
+      (nf == 1 ? hc->gamma : hc->min_half) = f;
+    }
+    if (c == std::string::npos) break;
+    pos = c + 1;
+  }
+  return hc->radius >= 0 && hc->radius <= 4 && hc->min_taps >= 1 && std::isfinite(hc->gamma) && hc->gamma >= 0 &&
+         std::isfinite(hc->min_half) && hc->min_half >= 0;
+}
+
 // --move SPEC: K:DX,DY,DZ -- an object index and three finite doubles
 static bool parse_move(const std::string& x, long long* k, double v[3]) {
   const size_t colon = x.find(':');
@@ -782,6 +825,9 @@ int main(int argc, char** argv) {
     double v[3];
   };
   std::vector<Move> moves;     // --move K:DX,DY,DZ, repeatable
+  bool clip_on = false;        // --clip SPEC
+  rt_history_clip hclip;
+  rt_history_clip_default(&hclip);
   bool temporal_on = false;    // --temporal SPEC
   rt_temporal tpar;
   rt_temporal_default(&tpar);
@@ -953,6 +999,14 @@ int main(int argc, char** argv) {
         return 2;
       }
       temporal_on = true;
+    } else if (a == "--clip") {  // --orbit --temporal: rectify the reprojected history
+      const std::string x = need("--clip");
+      if (!parse_clip(x, &hclip)) {
+        fprintf(stderr, "invalid --clip %s (default, or RADIUS[,GAMMA[,MIN_TAPS[,MIN_HALF]]]: radius 0..4, gamma >= 0, "
+                        "min_taps >= 1, min_half >= 0)\n", x.c_str());
+        return 2;
+      }
+      clip_on = true;
     } else if (a == "--move") {  // --orbit: object K is offset by f * (DX, DY, DZ) at view f
       const std::string x = need("--move");
       Move mv;
@@ -1003,6 +1057,10 @@ int main(int argc, char** argv) {
   }
   if (temporal_on && (orbit_n <= 0 || st.samples < 1)) {
     fprintf(stderr, "--temporal accumulates the views of --orbit and needs --samples >= 1\n");
+    return 2;
+  }
+  if (clip_on && (orbit_n <= 0 || !temporal_on)) {
+    fprintf(stderr, "--clip rectifies the history of --temporal and needs --orbit N --temporal SPEC\n");
     return 2;
   }
   if (!moves.empty() && orbit_n <= 0) {
@@ -1164,7 +1222,7 @@ int main(int argc, char** argv) {
     if (rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK ||
         render_orbit(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)orbit_n, orbit_deg, save, &stats,
                      temporal_on ? &tpar : nullptr, denoise_on && !variance_on ? &dn : nullptr,
-                     variance_on ? &vspec : nullptr, moves.empty() ? nullptr : move_table.data()) != RT_OK) {
+                     variance_on ? &vspec : nullptr, moves.empty() ? nullptr : move_table.data(), clip_on ? &hclip : nullptr) != RT_OK) {
       if (!save_failed) fprintf(stderr, "render failed: %s\n", rt_last_error());
       rt_scene_free(sb);
       return save_failed ? 1 : 2;

@@ -15,6 +15,7 @@
 #include "../../include/rt_api.h"
 #include "../../include/rt_temporal.h"
 #include "../../include/rt_variance.h"
+#include "../../include/rt_clip.h"
 #include "rt_scene_dev.h"
 
 namespace rtgo {
@@ -687,6 +688,18 @@ struct TemporalMotionParams {
 };
 int launch_temporal_motion(const TemporalMotionParams& p, void* stream);
 int preload_motion_kernels();
+
+// ---- temporal accumulation with history rectification (rt_clip.hip; rt_temporal_clip_async)
+struct TemporalClipParams {
+  TemporalMotionParams mo;     // motion null: no table (m = 0, ids optional); m.cur_albedo may be given without moments
+  rt_cl_params clip;           // checked
+  float* out_clipped;          // W*H, or null
+};
+// launch_temporal_clip takes the staged form from this radius on when RTGO_CLIP_FORM does not say (DESIGN.md
+// §4.18 has the A/B: at radius 1 the staged form's gain did not clear twice the spread in every case)
+constexpr int32_t kClipStagedFromRadius = 2;
+int launch_temporal_clip(const TemporalClipParams& p, void* stream);
+int preload_clip_kernels();
 
 // ---------------------------------------------------------------- wavefront path
 // (rt_wavefront.hip: BVH scenes)

@@ -313,6 +313,17 @@ class Motion(ctypes.Structure):
     ]
 
 
+class HistoryClip(ctypes.Structure):
+    """rt_history_clip: the parameters of history rectification (default_history_clip())."""
+
+    _fields_ = [
+        ("radius", ctypes.c_int32),
+        ("min_taps", ctypes.c_int32),
+        ("gamma", ctypes.c_double),
+        ("min_half", ctypes.c_double),
+    ]
+
+
 class Variance(ctypes.Structure):
     """rt_variance: the parameters of the variance pass (default_variance())."""
 
@@ -485,6 +496,9 @@ EXPORTED_SYMBOLS = [
     "rt_temporal_motion_async",
     "rt_temporal_motion_host",
     "rt_scene_motion",
+    "rt_history_clip_default",
+    "rt_temporal_clip_async",
+    "rt_temporal_clip_host",
 ]
 
 _lib = None
@@ -647,6 +661,13 @@ def lib():
                                                     vp, vp, vp]),
         "rt_scene_motion": (ctypes.c_int, [ctypes.POINTER(SceneView), ctypes.POINTER(SceneView),
                                             ctypes.POINTER(ctypes.c_double), sz]),
+        "rt_history_clip_default": (None, [ctypes.POINTER(HistoryClip)]),
+        "rt_temporal_clip_async": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
+                                                   ctypes.POINTER(TemporalFrame), ctypes.POINTER(Motion),
+                                                   ctypes.POINTER(HistoryClip), vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rt_temporal_clip_host": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
+                                                  ctypes.POINTER(TemporalFrame), ctypes.POINTER(Motion),
+                                                  ctypes.POINTER(HistoryClip), vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -776,6 +797,22 @@ class Scene:
         lights = [Light.from_buffer_copy(self._view.lights[k]) for k in range(self._view.num_lights)]
         return Scene(objects=objs, lights=lights, camera=Camera.from_buffer_copy(self._view.camera))
 
+    def relit(self, light_offsets) -> "Scene":
+        """A copy of the scene with light i moved by light_offsets[i] (a (num_lights, 3) array; DESIGN.md
+        §4.18): position + offset in binary64, everything else as it is."""
+        n = int(self._view.num_lights)
+        off = np.asarray(light_offsets, np.float64)
+        if off.shape != (n, 3) or not np.isfinite(off).all():
+            raise RenderError(f"Scene.relit: light_offsets are a finite ({n}, 3) array, one row per light")
+        objs = [Object.from_buffer_copy(self._view.objects[k]) for k in range(self.num_objects)]
+        lights = []
+        for i in range(n):
+            lt = Light.from_buffer_copy(self._view.lights[i])
+            for j in range(3):
+                lt.position[j] = lt.position[j] + float(off[i, j])
+            lights.append(lt)
+        return Scene(objects=objs, lights=lights, camera=Camera.from_buffer_copy(self._view.camera))
+
     def print_hittables(self):
         if self._handle is not None:
             lib().rt_scene_print_hittables(self._handle)
@@ -818,6 +855,7 @@ class ParallelRenderer:
         self.last_temporal_linear = None  # render_sequence(temporal=...): the accumulated frames (n x H x W x 3)
         self.last_history = None  # ... and each pixel's history length (n x H x W)
         self.last_variance = None  # variance=...: the variance pass's output (n x H x W, or H x W of render_denoised)
+        self.last_clipped = None  # render_sequence(clip=...): 1 where the history was clipped (n x H x W)
 
     def set_tuning(self, tuning: Tuning):
         self._tuning = tuning
@@ -1067,7 +1105,8 @@ class ParallelRenderer:
         return img
 
     def render_sequence(self, scene: Scene, width: int, height: int, cameras, seeds=None, temporal=None,
-                        denoise=None, variance=None, guide="first", specular=None, offsets=None) -> np.ndarray:
+                        denoise=None, variance=None, guide="first", specular=None, offsets=None, clip=None,
+                        light_offsets=None) -> np.ndarray:
         """The scene from each of ``cameras`` (Camera structs or scene-file camera dicts; any number):
         an (n, H, W, 4) uint8 array, frame f that of ``render`` with the scene's camera replaced by
         cameras[f] and seed seeds[f] (None: the renderer's seed), byte for byte.
@@ -1106,8 +1145,21 @@ class ParallelRenderer:
         the feature passes use the same scene.  With ``temporal`` the accumulation is
         rt_temporal_motion_async with scene_motion(frame f - 1's scene, frame f's) as its table, so that a
         moving object keeps its history; ``denoise``, ``variance`` and ``guide`` compose as above.  Without
-        ``offsets`` the method and its launches are what they were."""
+        ``offsets`` the method and its launches are what they were.
+
+        clip ("default" / True, a dict of HistoryClip's fields or a HistoryClip; §4.18; only together with
+        ``temporal``, with or without ``offsets``): the accumulation is rt_temporal_clip_async, which clips
+        each pixel's reprojected history to what the current frame's neighbourhood allows, demodulated by the
+        frame's albedo.  ``last_clipped`` is (n, H, W) float32, 1 where a channel was clipped.  It composes
+        with ``denoise``, ``variance`` and ``guide``.  With clip None nothing changes.
+
+        light_offsets (an (n, num_lights, 3) array; §4.18): frame f is the scene with light i moved by
+        light_offsets[f][i] (Scene.relit), rendered one by one as with ``offsets``, with which it composes.
+        Lights are not part of the motion table: a moving light is what ``clip`` is for."""
         t0 = time.perf_counter()
+        hc = None if clip is None or clip is False else _as_history_clip(clip)
+        if hc is not None and (temporal is None or temporal is False):
+            raise RenderError("render_sequence: clip rectifies the accumulated history and needs temporal")
         spec = _as_guide(guide, specular)
         tp = None if temporal is None or temporal is False else _as_temporal(temporal)
         dn = None if denoise is None or denoise is False else _as_denoise(denoise)
@@ -1133,14 +1185,25 @@ class ParallelRenderer:
         if seeds is None and tp is not None:
             seeds = [(int(self.settings.seed) + f) & (2 ** 64 - 1) for f in range(n)]
         scenes = None
+        if light_offsets is not None:
+            loff = np.asarray(light_offsets, np.float64)
+            if loff.shape != (n, int(scene.view.num_lights), 3) or not np.isfinite(loff).all():
+                raise RenderError(f"render_sequence: light_offsets have shape {loff.shape}, expected a finite "
+                                  f"({n}, {int(scene.view.num_lights)}, 3) array: one row per frame and light")
         if offsets is not None:
             off = np.asarray(offsets, np.float64)
             if off.shape != (n, scene.num_objects, 3):
                 raise RenderError(f"render_sequence: offsets have shape {off.shape}, expected "
                                   f"({n}, {scene.num_objects}, 3): one row per frame and object")
+        if light_offsets is not None and offsets is None:
+            off = np.zeros((n, scene.num_objects, 3), np.float64)
+        if offsets is not None or light_offsets is not None:
             scenes = [scene.translated(off[f]) for f in range(n)]
+            if light_offsets is not None:
+                scenes = [scenes[f].relit(loff[f]) for f in range(n)]
             tables = [np.zeros((max(1, scene.num_objects), 3), np.float64)]  # (frame 0 starts the history)
-            tables += [scene_motion(scenes[f - 1], scenes[f]) for f in range(1, n)]
+            tables += [scene_motion(scenes[f - 1], scenes[f]) if scene.num_objects > 0 else tables[0]
+                       for f in range(1, n)]
             if tp is not None and scene.num_objects < 1:
                 raise RenderError("render_sequence: offsets with temporal need a scene with objects")
         for s in (scenes if scenes is not None else [scene]):
@@ -1188,6 +1251,8 @@ class ParallelRenderer:
                     dlin = torch.zeros((n, npix * 3), dtype=torch.float32, device="cuda")
                     mom = torch.zeros((n, npix * 2), dtype=torch.float32, device="cuda")
                     var = torch.zeros((n, npix), dtype=torch.float32, device="cuda")
+                if hc is not None:
+                    clp = torch.zeros((n, npix), dtype=torch.float32, device="cuda")
                 if spec is not None:  # the spatial filter's guide; the accumulation keeps the first hits
                     sg = {k: torch.zeros_like(v) for k, v in feat[0].items()}
                 fst = Settings.from_buffer_copy(self.settings)
@@ -1209,8 +1274,20 @@ class ParallelRenderer:
                     cur = temporal_frame(camera_frame(cams[f], int(self.settings.camera), width, height),
                                          lin[f].data_ptr(), ft["depth"].data_ptr(), ft["object"].data_ptr(),
                                          ft["normal"].data_ptr())
+                    if hc is not None:  # (the same outputs as the branches below, by rt_temporal_clip_async)
+                        temporal_clip_async(width, height, cur, prev, acc[f].data_ptr(), cnt[f].data_ptr(),
+                                            None if vg is not None else rgba[f].data_ptr(), tp, 0, clip=hc,
+                                            d_motion=mot[f].data_ptr() if scenes is not None else None,
+                                            num_objects=mot[f].shape[0] if scenes is not None else 0,
+                                            d_cur_albedo=ft["albedo"].data_ptr(),
+                                            d_prev_moments=(mom[f - 1].data_ptr()
+                                                            if vg is not None and prev is not None else None),
+                                            d_out_moments=mom[f].data_ptr() if vg is not None else None,
+                                            d_out_clipped=clp[f].data_ptr())
                     if vg is not None:
-                        if scenes is not None:
+                        if hc is not None:
+                            pass
+                        elif scenes is not None:
                             temporal_motion_async(width, height, cur, prev, mot[f].data_ptr(), mot[f].shape[0],
                                                   acc[f].data_ptr(), cnt[f].data_ptr(), None, tp, 0,
                                                   d_cur_albedo=ft["albedo"].data_ptr(),
@@ -1227,6 +1304,8 @@ class ParallelRenderer:
                                           gd["depth"].data_ptr(), var[f].data_ptr(), gd["albedo"].data_ptr(),
                                           gd["object"].data_ptr(), dlin[f].data_ptr(), rgba[f].data_ptr(), None,
                                           work.data_ptr(), nbytes, vg[1], 0)
+                    elif hc is not None:
+                        pass
                     elif scenes is not None:
                         temporal_motion_async(width, height, cur, prev, mot[f].data_ptr(), mot[f].shape[0],
                                               acc[f].data_ptr(), cnt[f].data_ptr(), rgba[f].data_ptr(), tp, 0)
@@ -1246,6 +1325,7 @@ class ParallelRenderer:
             self.last_denoised_linear = (dlin.cpu().numpy().reshape(n, height, width, 3)
                                          if dn is not None or vg is not None else None)
             self.last_variance = var.cpu().numpy().reshape(n, height, width) if vg is not None else None
+            self.last_clipped = clp.cpu().numpy().reshape(n, height, width) if hc is not None else None
             img = rgba.cpu().numpy().reshape(n, height, width, 4)
         self.benchmark_data = {
             "scene_name": "demo_scene",
@@ -2104,6 +2184,87 @@ def temporal_motion_host(cur: dict, prev=None, motion=None, params=None, moments
                                          out.ctypes.data, cnt.ctypes.data, mom.ctypes.data if moments else None,
                                          rgba.ctypes.data))
     return (out, cnt, mom, rgba) if moments else (out, cnt, rgba)
+
+
+_HISTORY_CLIP_FIELDS = ("radius", "min_taps", "gamma", "min_half")
+
+
+def default_history_clip(**over) -> HistoryClip:
+    """rt_history_clip_default (radius 1, min_taps 5, gamma 1, min_half 0), with the given
+    fields replaced."""
+    c = HistoryClip()
+    lib().rt_history_clip_default(ctypes.byref(c))
+    for k, val in over.items():
+        if k not in _HISTORY_CLIP_FIELDS:
+            raise RenderError(f"default_history_clip: no such field {k}")
+        setattr(c, k, val)
+    return c
+
+
+def _as_history_clip(params) -> HistoryClip:
+    if isinstance(params, str) and params == "default":
+        return default_history_clip()
+    return _as_one(params, HistoryClip, default_history_clip, "clip")
+
+
+def temporal_clip_async(width: int, height: int, cur: TemporalFrame, prev, d_out_color: int, d_out_count: int,
+                        d_out_rgba=None, params=None, stream: int = 0, clip=None, d_motion=None, num_objects: int = 0,
+                        d_cur_albedo=None, d_prev_moments=None, d_out_moments=None, d_out_clipped=None):
+    """rt_temporal_clip_async: temporal_motion_async (d_motion None: temporal_async, or with
+    d_out_moments temporal_moments_async) whose reprojected history is clipped to mean +- gamma * sigma of the
+    current frame's neighbourhood.  clip: a HistoryClip, a dict of its fields or None (the defaults);
+    d_cur_albedo demodulates the window and may be given without moments; d_out_clipped (W*H floats, 1 where
+    a channel was clipped) is optional."""
+    p = _as_temporal(params)
+    c = _as_history_clip(clip)
+    m = Motion(d_motion, num_objects, 0) if d_motion is not None else None
+    _check(lib().rt_temporal_clip_async(ctypes.byref(p), width, height, ctypes.byref(cur),
+                                        ctypes.byref(prev) if prev is not None else None,
+                                        ctypes.byref(m) if m is not None else None, ctypes.byref(c),
+                                        ctypes.c_void_p(d_cur_albedo), ctypes.c_void_p(d_prev_moments),
+                                        ctypes.c_void_p(d_out_color), ctypes.c_void_p(d_out_count),
+                                        ctypes.c_void_p(d_out_moments), ctypes.c_void_p(d_out_clipped),
+                                        ctypes.c_void_p(d_out_rgba), ctypes.c_void_p(stream)))
+
+
+def temporal_clip_host(cur: dict, prev=None, motion=None, params=None, moments: bool = False, clip=None):
+    """rt_temporal_clip_host: temporal_motion_host (motion None: temporal_host / temporal_moments_host) with
+    history rectification.  cur may hold ``albedo`` with and without moments.  Returns (color, count, clipped
+    (H, W) float32, rgba), or (color, count, moments, clipped, rgba)."""
+    what = "temporal_clip_host"
+    color = np.ascontiguousarray(cur["color"], np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise RenderError(f"{what}: color is an (H, W, 3) array")
+    table = np.ascontiguousarray(motion, np.float64) if motion is not None else None
+    if table is not None and (table.ndim != 2 or table.shape[1] != 3):
+        raise RenderError(f"{what}: motion is a (num_objects, 3) array or None")
+    h, w = color.shape[:2]
+    keep = []
+
+    def frame_of(d, name):
+        a = _host_arrays(f"{what}: {name}", h, w, keep,
+                         color=(d.get("color"), np.float32, (h, w, 3)), depth=(d.get("depth"), np.float32, (h, w)),
+                         object=(d.get("object"), np.int32, (h, w)), normal=(d.get("normal"), np.float32, (h, w, 3)),
+                         count=(d.get("count"), np.float32, (h, w)), albedo=(d.get("albedo"), np.float32, (h, w, 3)),
+                         moments=(d.get("moments"), np.float32, (h, w, 2)))
+        return temporal_frame(d["frame"], a["color"], a["depth"], a["object"], a["normal"], a["count"]), a
+
+    fc, ac = frame_of(cur, "cur")
+    fp, ap = frame_of(prev, "prev") if prev is not None else (None, {"moments": None})
+    p = _as_temporal(params)
+    c = _as_history_clip(clip)
+    m = Motion(table.ctypes.data, table.shape[0], 0) if table is not None else None
+    out = np.zeros((h, w, 3), np.float32)
+    cnt = np.zeros((h, w), np.float32)
+    mom = np.zeros((h, w, 2), np.float32)
+    clp = np.zeros((h, w), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    _check(lib().rt_temporal_clip_host(ctypes.byref(p), w, h, ctypes.byref(fc),
+                                       ctypes.byref(fp) if fp is not None else None,
+                                       ctypes.byref(m) if m is not None else None, ctypes.byref(c), ac["albedo"],
+                                       ap["moments"] if moments else None, out.ctypes.data, cnt.ctypes.data,
+                                       mom.ctypes.data if moments else None, clp.ctypes.data, rgba.ctypes.data))
+    return (out, cnt, mom, clp, rgba) if moments else (out, cnt, clp, rgba)
 
 
 def variance_async(width: int, height: int, d_color: int, d_normal: int, d_depth: int, d_albedo=None, d_object=None,

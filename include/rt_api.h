@@ -1133,7 +1133,8 @@ int rt_denoise_var_host(const rt_denoise_var* params, int32_t width, int32_t hei
  * Known limits.  A static pixel under a moving object's shadow keeps its old
  * history, and what a moving mirror shows does not reproject (its lighting
  * changes as it moves; DESIGN.md §4.17 has the figures).  max_history bounds
- * both.  Rotations and deformations are not modelled. */
+ * both, and rt_temporal_clip_async (below) rectifies them.  Rotations and
+ * deformations are not modelled. */
 typedef struct {
   const double* motion;  /* num_objects * 3 */
   int32_t num_objects;
@@ -1150,6 +1151,98 @@ int rt_temporal_motion_host(const rt_temporal* params, int32_t width, int32_t he
                             const float* prev_moments, float* out_color, float* out_count, float* out_moments,
                             uint8_t* out_rgba);
 int rt_scene_motion(const rt_scene* prev, const rt_scene* cur, double* out, size_t capacity);
+
+/* History rectification: temporal accumulation that clips
+ * the reprojected history to what the current frame's neighbourhood allows.
+ * Every pass above reprojects geometry; none looks at whether the light a
+ * surface point receives has changed, so a static pixel under a moving shadow,
+ * what a moving mirror shows, a reflection under a moving camera and
+ * everything under a moving light keep a history that no longer holds.  Here
+ * the history colour is clipped to mean +- gamma * sigma of the demodulated
+ * colour around the pixel in the CURRENT frame (variance clipping) before the
+ * blend: a history the current frame contradicts by many sigma is pulled to
+ * the edge of that range, one that agrees is left alone to the bit.
+ *
+ * The arguments are rt_temporal_motion_async's plus `clip` (rt_history_clip;
+ * rt_history_clip_default) and the optional output out_clipped (float, W*H).
+ *   radius    the window is (2 * radius + 1)^2; 0 (off) to 4
+ *   min_taps  >= 1: no clip where the window has fewer valid taps
+ *   gamma     finite and >= 0: the range's half width in sigmas
+ *   min_half  finite and >= 0: added to the half width
+ * Anything else, NaN included, is RT_E_INVALID.
+ *
+ * `motion` may be NULL here: then m = 0 and `object` is optional (NULL in both
+ * frames or in neither), as in rt_temporal_async.  With a table ids are
+ * required, as in rt_temporal_motion_async.
+ *
+ * Per pixel p = (x, y), steps 1 to 5 and 7 are rt_temporal_motion_async's, or
+ * the moments form's when out_moments is given, bit for bit and in their
+ * order.  Between step 5 and step 6, only where step 5 found a history and
+ * radius > 0:
+ *   5a. The window.  e(q)[k] = rt_variance's e(cur.color[q], cur_albedo[q])[k]:
+ *       binary64 color / max(albedo, floor), the plain colour when cur_albedo
+ *       is NULL.  nw = 0, s1[3] = s2[3] = 0.  Taps q = (x + dx, y + dy), dy =
+ *       -r..r outer, dx = -r..r inner.  A tap is skipped when q is outside the
+ *       image, when cur.depth[q] is not finite, or when ids are given and
+ *       cur.object[q] != cur.object[p].  Otherwise nw += 1 and per k
+ *       s1[k] += e, s2[k] += e * e.  If nw < min_taps there is no clip.  Else
+ *       mu[k] = s1[k] / nw, var[k] = s2[k] / nw - mu[k] * mu[k],
+ *       var = var > 0 ? var : 0, half[k] = gamma * sqrt(var[k]) + min_half
+ *       (binary64 sqrt, correctly rounded).
+ *   5b. The clip.  hist[k] = sum[k] / sumw (step 6's value), fa[k] =
+ *       max(cur_albedo[p][k], floor) or 1 without albedo, he[k] = hist[k] /
+ *       fa[k], lo = mu[k] - half[k], hi = mu[k] + half[k],
+ *       hc[k] = he < lo ? lo : (he > hi ? hi : he); a NaN fails both
+ *       comparisons and stays.  Where hc[k] != he[k], step 6 blends with
+ *       hc[k] * fa[k] in that channel; where not, with hist[k] unchanged (no
+ *       round trip through the division).  (A NaN compares unequal to
+ *       itself: a NaN history is blended as hc * fa, a NaN again, and counts
+ *       as clipped.  A NaN mu or half clips nothing.)
+ *   out_clipped[p] = 1 when a channel was replaced, else 0; 0 for every pixel
+ *   without a history.
+ * n, the count and the moment sums are untouched: the moments keep the old
+ * frames, so the variance of a clipped pixel stays high and the
+ * variance-guided filter smooths it.
+ *   - radius = 0: every output equals rt_temporal_motion_async's bit for bit,
+ *     for every input; with motion = NULL, rt_temporal_async's or
+ *     rt_temporal_moments_async's.
+ *   - Every address comes from x, y, dx, dy and bounds checks; the one guarded
+ *     address from a pixel's value is the motion table's.
+ *
+ * cur_albedo.  It demodulates the window, so it may be given WITHOUT
+ * out_moments here (the one rule looser than the calls this extends);
+ * prev_moments without out_moments is refused as there.
+ *
+ * rt_temporal_clip_async: device pointers, no workspace, no context, no
+ * allocation; asynchronous on `hip_stream`.  RT_E_INVALID with a message,
+ * nothing enqueued and no buffer touched: whatever the call it extends refuses
+ * (rt_temporal_motion_async with a table, rt_temporal_async /
+ * rt_temporal_moments_async without), a NULL clip, a parameter out of range,
+ * out_clipped equal to another output.  rt_temporal_clip_host does the same
+ * with host pointers and no device.
+ *
+ * Known limits.  The range is as wide as the current frame's noise: at 1 spp a
+ * history inside mean +- gamma * sigma passes although it is stale, so slow
+ * changes (a soft shadow's edge, a rough reflection) are narrowed, not removed
+ * (DESIGN.md §4.18 and §9 have the figures). */
+typedef struct {
+  int32_t radius;
+  int32_t min_taps;
+  double gamma;
+  double min_half;
+} rt_history_clip;
+void rt_history_clip_default(rt_history_clip* c);
+int rt_temporal_clip_async(const rt_temporal* params, int32_t width, int32_t height, const rt_temporal_frame* cur,
+                           const rt_temporal_frame* prev /* NULL: start a history */,
+                           const rt_motion* motion /* device table; may be NULL */, const rt_history_clip* clip,
+                           const float* d_cur_albedo, const float* d_prev_moments, float* d_out_color,
+                           float* d_out_count, float* d_out_moments /* may be NULL */,
+                           float* d_out_clipped /* may be NULL */, uint8_t* d_out_rgba /* may be NULL */,
+                           void* hip_stream);
+int rt_temporal_clip_host(const rt_temporal* params, int32_t width, int32_t height, const rt_temporal_frame* cur,
+                          const rt_temporal_frame* prev, const rt_motion* motion, const rt_history_clip* clip,
+                          const float* cur_albedo, const float* prev_moments, float* out_color, float* out_count,
+                          float* out_moments, float* out_clipped, uint8_t* out_rgba);
 
 /* What a context has done so far (diagnostics): work schedules built (a new
  * scene, frame, rank or settings key; a measured re-cut counts too),
