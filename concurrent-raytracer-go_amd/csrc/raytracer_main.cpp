@@ -13,6 +13,8 @@
 //             [--aov-specular default|BOUNCES[,MAX_ROUGHNESS]]
 //             [--move K:DX,DY,DZ]...
 //             [--clip default|RADIUS[,GAMMA[,MIN_TAPS[,MIN_HALF]]]]
+//             [--matte PREFIX[,SAMPLES[,RANKS[,object|face]]]]
+//             [--edge-resolve default|SAMPLES[,RADIUS]]
 //
 // Same positional arguments, stdout lines, ".png" default extension
 // (main.go:53-56) and benchmark_data.json next to the output
@@ -109,6 +111,21 @@
 // demodulates it).  SPEC is `default` (rt_history_clip_default) or up to four
 // comma-separated fields that replace the defaults from the left.  It combines
 // with --move, --denoise, --denoise-variance and --aov-specular as above.
+// --matte PREFIX[,SAMPLES[,RANKS[,object|face]]] (one view, a
+// size with pixels) writes, after the render, the matte layers of the frame
+// (rt_context_render_matte_async with SAMPLES (16) camera rays per pixel, RANKS
+// (4) ranks, the render's seed and camera model; device 0) as PREFIX.id<r> and
+// PREFIX.coverage<r> for each rank r and PREFIX.rest, with the output image's
+// extension: id in --aov's object colours of the key (an empty rank black),
+// coverage grey round(count / SAMPLES * 255), rest grey round(rest / SAMPLES *
+// 255).
+// --edge-resolve SPEC (one view, --samples >= 1, a size with
+// pixels) antialiases the silhouettes of the image written: the frame's linear
+// image -- the filter's with --denoise or --denoise-variance -- goes through
+// rt_matte_resolve_async with an object-level matte of SAMPLES camera rays per
+// pixel (4 ranks) and the frame's first-hit object ids (the render's samples,
+// or those of the first pass with --pass-samples).  SPEC is `default` (16
+// samples, radius 2) or SAMPLES[,RADIUS].
 #include <errno.h>
 #include <math.h>
 #include <stdio.h>
@@ -642,14 +659,145 @@ static int write_aov(const rt_scene* scene, int32_t w, int32_t h, const rt_setti
   return RT_OK;
 }
 
+// --edge-resolve: the matte's samples and the resolve's parameters.
+struct EdgeResolve {
+  int32_t samples;
+  rt_matte_resolve rs;
+};
+// The resolve of the device image d_color into d_rgba on ctx's device: an object-level matte of the frame
+// (er.samples rays per pixel, 4 ranks, st's seed and camera model), the frame's first-hit ids (d_object, or when
+// that is null a first-hit pass with feature_samples samples) and rt_matte_resolve_async.
+static int edge_resolve_device(rt_context* ctx, int32_t w, int32_t h, const rt_settings& st, int feature_samples,
+                               const EdgeResolve& er, const float* d_color, const int32_t* d_object, uint8_t* d_rgba) {
+  const size_t npix = (size_t)w * (size_t)h;
+  rt_matte mp;
+  rt_matte_default(&mp);
+  int32_t* d = nullptr;  // id | count | rest | object
+  if (hipMalloc((void**)&d, npix * (size_t)(2 * mp.ranks + 2) * sizeof(int32_t)) != hipSuccess) {
+    fprintf(stderr, "hipMalloc failed\n");
+    return RT_E_DEVICE;
+  }
+  int32_t *d_id = d, *d_count = d + npix * (size_t)mp.ranks, *d_rest = d + npix * (size_t)(2 * mp.ranks);
+  int rc = RT_OK;
+  if (!d_object) {
+    rt_settings fst = st;
+    fst.samples = feature_samples;
+    const rt_aov_buffers out = {nullptr, nullptr, nullptr, nullptr, d_rest + npix};
+    rc = rt_context_render_aov_async(ctx, w, h, &fst, nullptr, &out, nullptr);
+    d_object = d_rest + npix;
+  }
+  if (rc == RT_OK) {
+    rt_settings mst = st;
+    mst.samples = er.samples;
+    const rt_matte_buffers out = {d_id, d_count, d_rest};
+    rc = rt_context_render_matte_async(ctx, w, h, &mst, nullptr, &mp, &out, nullptr);
+  }
+  if (rc == RT_OK) {
+    const rt_matte_resolve_inputs in = {d_color, d_object, d_id, d_count, d_rest, mp.ranks, er.samples};
+    rc = rt_matte_resolve_async(&er.rs, w, h, &in, nullptr, d_rgba, nullptr);
+  }
+  if (rc == RT_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = RT_E_DEVICE;
+  const std::string err = rc != RT_OK ? rt_last_error() : "";
+  (void)hipFree(d);
+  if (rc != RT_OK && !err.empty()) fprintf(stderr, "%s\n", err.c_str());
+  return rc;
+}
+
+// --edge-resolve without a filter: the frame's linear radiance `linear` (host, w*h*3) resolved on device 0 into
+// rgba (host, w*h*4).
+static int resolve_image(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int feature_samples,
+                         const EdgeResolve& er, const float* linear, uint8_t* rgba) {
+  const size_t npix = (size_t)w * (size_t)h;
+  rt_context* ctx = nullptr;
+  int rc = rt_context_create(0, &ctx);
+  if (rc != RT_OK) return rc;
+  rc = rt_context_set_scene(ctx, scene, 0);
+  float* d = nullptr;
+  uint8_t* d_rgba = nullptr;
+  if (rc == RT_OK && (hipMalloc((void**)&d, npix * 3 * sizeof(float)) != hipSuccess ||
+                      hipMalloc((void**)&d_rgba, npix * 4) != hipSuccess ||
+                      hipMemcpy(d, linear, npix * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) {
+    fprintf(stderr, "hipMalloc or hipMemcpy failed\n");
+    rc = RT_E_DEVICE;
+  }
+  if (rc == RT_OK) rc = edge_resolve_device(ctx, w, h, st, feature_samples, er, d, nullptr, d_rgba);
+  if (rc == RT_OK && hipMemcpy(rgba, d_rgba, npix * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = RT_E_DEVICE;
+  for (void* p : {(void*)d, (void*)d_rgba})
+    if (p) (void)hipFree(p);
+  rt_context_destroy(ctx);
+  return rc;
+}
+
+// --matte: the matte layers of the frame on device 0 (rt_context_render_matte_async), written as
+// PREFIX.id<r>, PREFIX.coverage<r> and PREFIX.rest with the mappings of the usage text above.
+static int write_matte(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, const rt_matte& mp,
+                       int32_t samples, const std::string& prefix, const std::string& ext) {
+  const size_t npix = (size_t)w * (size_t)h, planes = (size_t)(2 * mp.ranks + 1);
+  rt_context* ctx = nullptr;
+  int rc = rt_context_create(0, &ctx);
+  if (rc != RT_OK) return rc;
+  rc = rt_context_set_scene(ctx, scene, 0);
+  int32_t* d = nullptr;
+  std::vector<int32_t> host(npix * planes);
+  if (rc == RT_OK && hipMalloc((void**)&d, npix * planes * sizeof(int32_t)) != hipSuccess) {
+    fprintf(stderr, "hipMalloc failed\n");
+    rc = RT_E_DEVICE;
+  }
+  if (rc == RT_OK) {
+    rt_settings mst = st;
+    mst.samples = samples;
+    const rt_matte_buffers out = {d, d + npix * (size_t)mp.ranks, d + npix * (size_t)(2 * mp.ranks)};
+    rc = rt_context_render_matte_async(ctx, w, h, &mst, nullptr, &mp, &out, nullptr);
+  }
+  if (rc == RT_OK && hipMemcpy(host.data(), d, npix * planes * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+    fprintf(stderr, "hipMemcpy failed\n");
+    rc = RT_E_DEVICE;
+  }
+  const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
+  if (d) (void)hipFree(d);
+  rt_context_destroy(ctx);
+  if (rc != RT_OK) {
+    if (!err.empty()) fprintf(stderr, "%s\n", err.c_str());
+    return rc;
+  }
+  std::vector<uint8_t> img(npix * 4);
+  for (size_t k = 0; k < planes; ++k) {
+    const int32_t* v = host.data() + k * npix;
+    const bool is_id = k < (size_t)mp.ranks;
+    for (size_t i = 0; i < npix; ++i) {
+      uint8_t* px = &img[4 * i];
+      px[3] = 255;
+      if (is_id) {
+        const uint32_t hsh = ((uint32_t)v[i] + 1u) * 2654435761u;
+        for (int c = 0; c < 3; ++c) px[c] = v[i] < 0 ? 0 : (uint8_t)(((hsh >> (8 * c)) & 0xFFu) | 0x80u);
+      } else {
+        px[0] = px[1] = px[2] = aov_byte((double)v[i] / (double)samples);
+      }
+    }
+    const std::string name = k == planes - 1 ? std::string("rest")
+                                             : (is_id ? "id" + std::to_string(k) : "coverage" + std::to_string(k - (size_t)mp.ranks));
+    const std::string fp = prefix + "." + name + ext;
+    printf("Saving to: %s\n", fp.c_str());
+    fflush(stdout);
+    rc = ext == ".ppm" ? rt_write_ppm(fp.c_str(), img.data(), w, h) : rt_write_png(fp.c_str(), img.data(), w, h);
+    if (rc != RT_OK) {
+      printf("Error saving image: %s\n", rt_last_error());
+      return rc;
+    }
+  }
+  return RT_OK;
+}
+
 // --denoise: the à-trous filter (rt_denoise_async) over the
 // frame's linear radiance `linear` (host, w*h*3) on device 0: the first-hit
 // feature buffers of the frame with feature_samples samples (st's seed and
 // camera model), then the filter; rgba (host, w*h*4) receives its tone-mapped
 // output.  vs (--denoise-variance): the filter is
-// rt_denoise_var_async, steered by rt_variance_async's spatial estimate.
+// rt_denoise_var_async, steered by rt_variance_async's spatial estimate.  er (--edge-resolve): the
+// filter's linear output goes through the edge resolve, whose image rgba then receives.
 static int denoise_image(const rt_scene* scene, int32_t w, int32_t h, const rt_settings& st, int feature_samples,
-                         const rt_denoise& dn, const float* linear, uint8_t* rgba, const VarianceSpec* vs = nullptr) {
+                         const rt_denoise& dn, const float* linear, uint8_t* rgba, const VarianceSpec* vs = nullptr,
+                         const EdgeResolve* er = nullptr) {
   const size_t npix = (size_t)w * (size_t)h;
   rt_context* ctx = nullptr;
   int rc = rt_context_create(0, &ctx);
@@ -659,6 +807,7 @@ static int denoise_image(const rt_scene* scene, int32_t w, int32_t h, const rt_s
   float* d = nullptr;
   uint8_t* d_rgba = nullptr;
   void* d_work = nullptr;
+  float* d_den = nullptr;  // the filter's linear output, with --edge-resolve only
   const size_t work_bytes = vs ? rt_denoise_var_workspace_bytes(w, h) : rt_denoise_workspace_bytes(w, h);
   auto hip_ok = [&](hipError_t e, const char* what) {
     if (e == hipSuccess) return true;
@@ -669,6 +818,7 @@ static int denoise_image(const rt_scene* scene, int32_t w, int32_t h, const rt_s
   if (rc == RT_OK && hip_ok(hipMalloc((void**)&d, npix * 12 * sizeof(float)), "hipMalloc") &&
       hip_ok(hipMalloc((void**)&d_rgba, npix * 4), "hipMalloc") && hip_ok(hipMalloc(&d_work, work_bytes), "hipMalloc"))
     hip_ok(hipMemcpy(d, linear, npix * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
+  if (rc == RT_OK && er) hip_ok(hipMalloc((void**)&d_den, npix * 3 * sizeof(float)), "hipMalloc");
   if (rc == RT_OK) {
     rt_settings fst = st;
     fst.samples = feature_samples;
@@ -680,14 +830,18 @@ static int denoise_image(const rt_scene* scene, int32_t w, int32_t h, const rt_s
       const rt_variance_inputs vin = {in.color, in.normal, in.depth, in.albedo, in.object, nullptr, nullptr};
       rc = rt_variance_async(&vs->vr, w, h, &vin, d + npix * 11, nullptr);
       if (rc == RT_OK)
-        rc = rt_denoise_var_async(&vs->dv, w, h, &in, d + npix * 11, nullptr, d_rgba, nullptr, d_work, work_bytes, nullptr);
+        rc = rt_denoise_var_async(&vs->dv, w, h, &in, d + npix * 11, d_den, d_rgba, nullptr, d_work, work_bytes, nullptr);
     } else {
-      rc = rt_denoise_async(&dn, w, h, &in, nullptr, d_rgba, d_work, work_bytes, nullptr);
+      rc = rt_denoise_async(&dn, w, h, &in, d_den, d_rgba, d_work, work_bytes, nullptr);
     }
   }
+  // (the first-hit ids: the guide's own unless it looked through the mirrors)
+  if (rc == RT_OK && er)
+    rc = edge_resolve_device(ctx, w, h, st, feature_samples, *er, d_den,
+                             g_spec_on ? nullptr : (const int32_t*)(d + npix * 10), d_rgba);
   if (rc == RT_OK) hip_ok(hipMemcpy(rgba, d_rgba, npix * 4, hipMemcpyDeviceToHost), "hipMemcpy");
   const std::string err = rc != RT_OK ? rt_last_error() : "";  // (before the clean-up's calls)
-  for (void* p : {(void*)d, (void*)d_rgba, d_work})
+  for (void* p : {(void*)d, (void*)d_rgba, d_work, (void*)d_den})
     if (p) (void)hipFree(p);
   rt_context_destroy(ctx);
   if (rc != RT_OK && !err.empty()) fprintf(stderr, "%s\n", err.c_str());
@@ -799,6 +953,52 @@ static bool parse_clip(const std::string& x, rt_history_clip* hc) {
          std::isfinite(hc->min_half) && hc->min_half >= 0;
 }
 
+// --edge-resolve SPEC: `default`, or SAMPLES[,RADIUS] over 16 and rt_matte_resolve_default's radius
+static bool parse_edge_resolve(const std::string& x, EdgeResolve* er) {
+  er->samples = 16;
+  rt_matte_resolve_default(&er->rs);
+  if (x == "default") return true;
+  if (x.empty()) return false;
+  const size_t c = x.find(',');
+  long long v = 0;
+  if (!parse_int(x.substr(0, c).c_str(), &v) || v < 1 || v > (1 << 24)) return false;
+  er->samples = (int32_t)v;
+  if (c != std::string::npos) {
+    if (!parse_int(x.substr(c + 1).c_str(), &v) || v < 1 || v > 4) return false;
+    er->rs.radius = (int32_t)v;
+  }
+  return true;
+}
+
+// --matte SPEC: PREFIX[,SAMPLES[,RANKS[,object|face]]] over 16 samples and rt_matte_default
+static bool parse_matte(const std::string& x, std::string* prefix, int32_t* samples, rt_matte* mp) {
+  *samples = 16;
+  rt_matte_default(mp);
+  size_t pos = 0;
+  for (int nf = 0;; ++nf) {
+    if (nf == 4) return false;  // a fifth field
+    const size_t c = x.find(',', pos);
+    const std::string part = x.substr(pos, c == std::string::npos ? std::string::npos : c - pos);
+    long long v = 0;
+    if (nf == 0) {
+      if (part.empty()) return false;
+      *prefix = part;
+    } else if (nf == 1) {
+      if (!parse_int(part.c_str(), &v) || v < 1 || v > (1 << 24)) return false;
+      *samples = (int32_t)v;
+    } else if (nf == 2) {
+      if (!parse_int(part.c_str(), &v) || v < 1 || v > RT_MATTE_MAX_RANKS) return false;
+      mp->ranks = (int32_t)v;
+    } else if (part == "object" || part == "face") {
+      mp->level = part == "face" ? RT_MATTE_FACE : RT_MATTE_OBJECT;
+    } else {
+      return false;
+    }
+    if (c == std::string::npos) return true;
+    pos = c + 1;
+  }
+}
+
 // --move SPEC: K:DX,DY,DZ -- an object index and three finite doubles
 static bool parse_move(const std::string& x, long long* k, double v[3]) {
   const size_t colon = x.find(':');
@@ -839,6 +1039,12 @@ int main(int argc, char** argv) {
   rt_denoise_var_default(&vspec.dv);
   rt_variance_default(&vspec.vr);
   std::string aov_prefix;      // --aov PREFIX (empty: no feature buffers)
+  std::string matte_prefix;    // --matte PREFIX[,...] (empty: no matte layers)
+  int32_t matte_samples = 16;
+  rt_matte mpar;
+  rt_matte_default(&mpar);
+  bool resolve_on = false;     // --edge-resolve SPEC
+  EdgeResolve eres;
   long long orbit_n = 0;       // --orbit N[,DEGREES] (0: one render)
   double orbit_deg = 360.0;
   double watchdog_s = 0;  // --watchdog (0: no bound, as Go's Render)
@@ -953,6 +1159,19 @@ int main(int argc, char** argv) {
         fprintf(stderr, "invalid --aov (a file name prefix)\n");
         return 2;
       }
+    } else if (a == "--matte") {  // the matte layers as images PREFIX.id<r>, .coverage<r>, .rest
+      const std::string x = need("--matte");
+      if (!parse_matte(x, &matte_prefix, &matte_samples, &mpar)) {
+        fprintf(stderr, "invalid --matte %s (PREFIX[,SAMPLES[,RANKS[,object|face]]]: samples >= 1, ranks 1..8)\n", x.c_str());
+        return 2;
+      }
+    } else if (a == "--edge-resolve") {  // antialias the written image's silhouettes
+      const std::string x = need("--edge-resolve");
+      if (!parse_edge_resolve(x, &eres)) {
+        fprintf(stderr, "invalid --edge-resolve %s (default, or SAMPLES[,RADIUS]: samples >= 1, radius 1..4)\n", x.c_str());
+        return 2;
+      }
+      resolve_on = true;
     } else if (a == "--aov-specular") {  // the feature pass follows mirrors
       const std::string x = need("--aov-specular");
       rt_aov_spec_default(&g_spec);
@@ -1055,6 +1274,14 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--aov-specular picks the feature pass of --aov, --denoise or --denoise-variance: give one of them\n");
     return 2;
   }
+  if ((resolve_on || !matte_prefix.empty()) && orbit_n > 0) {
+    fprintf(stderr, "--matte and --edge-resolve need one view (not with --orbit)\n");
+    return 2;
+  }
+  if (resolve_on && st.samples < 1) {
+    fprintf(stderr, "--edge-resolve needs --samples >= 1\n");
+    return 2;
+  }
   if (temporal_on && (orbit_n <= 0 || st.samples < 1)) {
     fprintf(stderr, "--temporal accumulates the views of --orbit and needs --samples >= 1\n");
     return 2;
@@ -1117,6 +1344,11 @@ int main(int argc, char** argv) {
     fprintf(stderr, "%s needs a size with pixels (%lldx%lld)\n", variance_on ? "--denoise-variance" : "--denoise", w, h);
     return 2;
   }
+  if ((resolve_on || !matte_prefix.empty()) && (w <= 0 || h <= 0)) {
+    fprintf(stderr, "--matte and --edge-resolve need a size with pixels (%lldx%lld)\n", w, h);
+    return 2;
+  }
+  const bool keep_linear = denoise_on || resolve_on;  // (the frame's linear image on the host)
   printf("Loading scene from: %s\n", scene_file.c_str());
   rt_scene_buf* sb = nullptr;
   if (rt_scene_load_json(scene_file.c_str(), 0, &sb) != RT_OK) {
@@ -1184,7 +1416,7 @@ int main(int argc, char** argv) {
     return 0;
   }
   // (--denoise holds the frame's linear image on the host: sized only for a frame that will render)
-  if (denoise_on && (w > 65536 || h > 65536 || rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK)) {
+  if (keep_linear && (w > 65536 || h > 65536 || rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK)) {
     fprintf(stderr, "render failed: %s\n", w > 65536 || h > 65536 ? "invalid image size" : rt_last_error());
     rt_scene_free(sb);
     return 2;
@@ -1241,11 +1473,11 @@ int main(int argc, char** argv) {
     memset(&stats, 0, sizeof stats);
     int rendered = 0;
     double mean_samples = -1;
-    std::vector<float> linear(denoise_on ? (size_t)w * (size_t)h * 3 : 0);
+    std::vector<float> linear(keep_linear ? (size_t)w * (size_t)h * 3 : 0);
     if (rt_validate(rt_scene_view(sb), (int32_t)w, (int32_t)h, &st) != RT_OK ||
         render_progressive(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)pass_samples, budget_s, converge,
                            adaptive_on ? &adapt : nullptr, count_map, rgba.data(), &stats, &rendered,
-                           &mean_samples, denoise_on ? linear.data() : nullptr) != RT_OK) {
+                           &mean_samples, keep_linear ? linear.data() : nullptr) != RT_OK) {
       fprintf(stderr, "render failed: %s\n", rt_last_error());
       rt_scene_free(sb);
       return 2;
@@ -1253,8 +1485,15 @@ int main(int argc, char** argv) {
     // (the features of the first pass's samples, as ParallelRenderer.render_progressive takes them)
     if (denoise_on && denoise_image(rt_scene_view(sb), (int32_t)w, (int32_t)h, st,
                                     (int)std::min<long long>(st.samples, pass_samples), dn, linear.data(),
-                                    rgba.data()) != RT_OK) {
+                                    rgba.data(), nullptr, resolve_on ? &eres : nullptr) != RT_OK) {
       fprintf(stderr, "denoise failed: %s\n", rt_last_error());
+      rt_scene_free(sb);
+      return 2;
+    }
+    if (resolve_on && !denoise_on &&
+        resolve_image(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, (int)std::min<long long>(st.samples, pass_samples),
+                      eres, linear.data(), rgba.data()) != RT_OK) {
+      fprintf(stderr, "edge resolve failed: %s\n", rt_last_error());
       rt_scene_free(sb);
       return 2;
     }
@@ -1272,6 +1511,11 @@ int main(int argc, char** argv) {
     }
     if (!aov_prefix.empty() &&
         write_aov(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, aov_prefix, ext_of(out_path)) != RT_OK) {
+      rt_scene_free(sb);
+      return 1;
+    }
+    if (!matte_prefix.empty() && write_matte(rt_scene_view(sb), (int32_t)w, (int32_t)h, st, mpar, matte_samples,
+                                             matte_prefix, ext_of(out_path)) != RT_OK) {
       rt_scene_free(sb);
       return 1;
     }
@@ -1304,8 +1548,8 @@ int main(int argc, char** argv) {
   memset(&stats, 0, sizeof stats);
   // img := renderer.Render(scene, width, height) (main.go:51): timed by
   // Render itself (renderer.go:68,101: stats.render_seconds)
-  std::vector<float> linear(denoise_on ? npix * 3 : 0);
-  int rc = rt_renderer_render(rr, scene, (int32_t)w, (int32_t)h, &st, denoise_on ? linear.data() : nullptr, rgba.data(),
+  std::vector<float> linear(keep_linear ? npix * 3 : 0);
+  int rc = rt_renderer_render(rr, scene, (int32_t)w, (int32_t)h, &st, keep_linear ? linear.data() : nullptr, rgba.data(),
                               &stats);
   if (rc != RT_OK) {
     fprintf(stderr, "render failed: %s\n", rt_last_error());
@@ -1315,8 +1559,15 @@ int main(int argc, char** argv) {
   }
   if (denoise_on &&
       denoise_image(scene, (int32_t)w, (int32_t)h, st, st.samples, dn, linear.data(), rgba.data(),
-                    variance_on ? &vspec : nullptr) != RT_OK) {
+                    variance_on ? &vspec : nullptr, resolve_on ? &eres : nullptr) != RT_OK) {
     fprintf(stderr, "denoise failed: %s\n", rt_last_error());
+    rt_renderer_destroy(rr);
+    rt_scene_free(sb);
+    return 2;
+  }
+  if (resolve_on && !denoise_on &&
+      resolve_image(scene, (int32_t)w, (int32_t)h, st, st.samples, eres, linear.data(), rgba.data()) != RT_OK) {
+    fprintf(stderr, "edge resolve failed: %s\n", rt_last_error());
     rt_renderer_destroy(rr);
     rt_scene_free(sb);
     return 2;
@@ -1337,6 +1588,12 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (!aov_prefix.empty() && write_aov(scene, (int32_t)w, (int32_t)h, st, aov_prefix, ext_of(out_path)) != RT_OK) {
+    rt_renderer_destroy(rr);
+    rt_scene_free(sb);
+    return 1;
+  }
+  if (!matte_prefix.empty() &&
+      write_matte(scene, (int32_t)w, (int32_t)h, st, mpar, matte_samples, matte_prefix, ext_of(out_path)) != RT_OK) {
     rt_renderer_destroy(rr);
     rt_scene_free(sb);
     return 1;

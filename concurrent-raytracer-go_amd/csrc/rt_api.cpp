@@ -369,6 +369,7 @@ int rt_context_create(int32_t device, rt_context** out) {
       if (e == hipSuccess) e = (hipError_t)preload_variance_kernels();
       if (e == hipSuccess) e = (hipError_t)preload_motion_kernels();
       if (e == hipSuccess) e = (hipError_t)preload_clip_kernels();
+      if (e == hipSuccess) e = (hipError_t)preload_matte_kernels();
       if (e != hipSuccess) {
         set_error(std::string("kernel code object load failed: ") + hipGetErrorString(e));
         return RT_E_DEVICE;

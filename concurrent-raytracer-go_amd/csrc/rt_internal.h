@@ -16,6 +16,7 @@
 #include "../../include/rt_temporal.h"
 #include "../../include/rt_variance.h"
 #include "../../include/rt_clip.h"
+#include "../../include/rt_matte.h"
 #include "rt_scene_dev.h"
 
 namespace rtgo {
@@ -700,6 +701,30 @@ struct TemporalClipParams {
 constexpr int32_t kClipStagedFromRadius = 2;
 int launch_temporal_clip(const TemporalClipParams& p, void* stream);
 int preload_clip_kernels();
+
+// ---- matte layers and the edge resolve (rt_matte.hip; rt_context_render_matte_async, rt_matte_resolve_async,
+// DESIGN.md §4.19)
+struct MatteParams {
+  AovParams a;                 // the first-hit pass's rays and scene (aov_setup); its five outputs stay null
+  int32_t level;               // checked: RT_MATTE_OBJECT or RT_MATTE_FACE
+  int32_t ranks;               // checked: 1..8
+  int32_t* id;                 // ranks * W*H, or null
+  int32_t* count;              // ranks * W*H, or null
+  int32_t* rest;               // W*H, or null
+};
+struct MatteResolveParams {
+  rt_mt_resolve_params r;      // checked (rt_mt_resolve_ok, the size rule)
+  const float* color;          // W*H*3
+  const int32_t* object;       // W*H
+  const int32_t* id;           // K * W*H
+  const int32_t* count;        // K * W*H
+  const int32_t* rest;         // W*H, or null
+  float* out_linear;           // W*H*3, not color; or null
+  uint8_t* out_rgba;           // W*H*4, or null
+};
+int launch_matte(const MatteParams& p, void* stream);
+int launch_matte_resolve(const MatteResolveParams& p, void* stream);
+int preload_matte_kernels();
 
 // ---------------------------------------------------------------- wavefront path
 // (rt_wavefront.hip: BVH scenes)

@@ -892,6 +892,52 @@ int rt_context_render_aov_spec_async(rt_context* c, int32_t w, int32_t h, const 
   return leave_stream(c, s);
 }
 
+// Matte layers (include/rt_api.h): the same call around
+// rt_matte.hip's matte_kernel.
+void rt_matte_default(rt_matte* m) {
+  if (!m) return;
+  memset(m, 0, sizeof *m);
+  m->ranks = 4;
+  m->level = RT_MATTE_OBJECT;
+}
+
+int rt_context_render_matte_async(rt_context* c, int32_t w, int32_t h, const rt_settings* st, const rt_camera* camera,
+                                  const rt_matte* params, const rt_matte_buffers* out, void* stream) {
+  if (!c || !st || !out || !params) {
+    set_error("rt_context_render_matte_async: context, settings, params or out is NULL");
+    return RT_E_INVALID;
+  }
+  if (params->ranks < 1 || params->ranks > RT_MATTE_MAX_RANKS ||
+      (params->level != RT_MATTE_OBJECT && params->level != RT_MATTE_FACE)) {
+    set_error("rt_context_render_matte_async: ranks must be in 1..8 and level RT_MATTE_OBJECT or RT_MATTE_FACE");
+    return RT_E_INVALID;
+  }
+  if (!out->d_id && !out->d_count && !out->d_rest) {
+    set_error("rt_context_render_matte_async: every buffer of out is NULL");
+    return RT_E_INVALID;
+  }
+  MatteParams q;
+  memset(&q, 0, sizeof q);
+  int rc = aov_setup(c, w, h, st, camera, "rt_context_render_matte_async", &q.a);
+  if (rc) return rc;
+  if (params->level == RT_MATTE_FACE && c->flat.objects >= (1 << 27)) {
+    set_error("rt_context_render_matte_async: the face level serves scenes of fewer than 2^27 objects");
+    return RT_E_INVALID;
+  }
+  q.level = params->level;
+  q.ranks = params->ranks;
+  q.id = out->d_id;
+  q.count = out->d_count;
+  q.rest = out->d_rest;
+  hipStream_t s = (hipStream_t)stream;
+  rc = enter_stream(c, s);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  const int e = launch_matte(q, s);
+  if (e != hipSuccess) return launch_failed("matte layers", e);
+  return leave_stream(c, s);
+}
+
 // rt_camera_orbit (include/rt_api.h states the formula and its order)
 int rt_camera_orbit(const rt_camera* cam, int32_t n, double degrees, rt_camera* out) {
   if (!cam || !out || n < 1) {

@@ -324,6 +324,55 @@ class HistoryClip(ctypes.Structure):
     ]
 
 
+class Matte(ctypes.Structure):
+    """rt_matte: the parameters of the matte pass (default_matte())."""
+
+    _fields_ = [
+        ("ranks", ctypes.c_int32),
+        ("level", ctypes.c_int32),
+    ]
+
+
+class MatteBuffers(ctypes.Structure):
+    """rt_matte_buffers: the device pointers of a matte pass (None / 0: not written); d_id and d_count are
+    ``ranks`` planes of W*H int32, d_rest one."""
+
+    _fields_ = [
+        ("d_id", ctypes.c_void_p),
+        ("d_count", ctypes.c_void_p),
+        ("d_rest", ctypes.c_void_p),
+    ]
+
+
+class MatteResolve(ctypes.Structure):
+    """rt_matte_resolve: the parameters of the edge resolve (default_matte_resolve())."""
+
+    _fields_ = [
+        ("radius", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+        ("background", ctypes.c_double * 3),
+    ]
+
+
+class MatteResolveInputs(ctypes.Structure):
+    """rt_matte_resolve_inputs: color, object, id and count are required; rest may be None / 0."""
+
+    _fields_ = [
+        ("color", ctypes.c_void_p),
+        ("object", ctypes.c_void_p),
+        ("id", ctypes.c_void_p),
+        ("count", ctypes.c_void_p),
+        ("rest", ctypes.c_void_p),
+        ("ranks", ctypes.c_int32),
+        ("samples", ctypes.c_int32),
+    ]
+
+
+RT_MATTE_SLOTS, RT_MATTE_MAX_RANKS = 16, 8
+RT_MATTE_OBJECT, RT_MATTE_FACE = 0, 1
+MATTE_LEVELS = {"object": RT_MATTE_OBJECT, "face": RT_MATTE_FACE}
+
+
 class Variance(ctypes.Structure):
     """rt_variance: the parameters of the variance pass (default_variance())."""
 
@@ -499,6 +548,11 @@ EXPORTED_SYMBOLS = [
     "rt_history_clip_default",
     "rt_temporal_clip_async",
     "rt_temporal_clip_host",
+    "rt_matte_default",
+    "rt_context_render_matte_async",
+    "rt_matte_resolve_default",
+    "rt_matte_resolve_async",
+    "rt_matte_resolve_host",
 ]
 
 _lib = None
@@ -668,6 +722,14 @@ def lib():
         "rt_temporal_clip_host": (ctypes.c_int, [ctypes.POINTER(Temporal), i32, i32, ctypes.POINTER(TemporalFrame),
                                                   ctypes.POINTER(TemporalFrame), ctypes.POINTER(Motion),
                                                   ctypes.POINTER(HistoryClip), vp, vp, vp, vp, vp, vp, vp]),
+        "rt_matte_default": (None, [ctypes.POINTER(Matte)]),
+        "rt_context_render_matte_async": (ctypes.c_int, [vp, i32, i32, ctypes.POINTER(Settings), ctypes.POINTER(Camera),
+                                                         ctypes.POINTER(Matte), ctypes.POINTER(MatteBuffers), vp]),
+        "rt_matte_resolve_default": (None, [ctypes.POINTER(MatteResolve)]),
+        "rt_matte_resolve_async": (ctypes.c_int, [ctypes.POINTER(MatteResolve), i32, i32,
+                                                   ctypes.POINTER(MatteResolveInputs), vp, vp, vp]),
+        "rt_matte_resolve_host": (ctypes.c_int, [ctypes.POINTER(MatteResolve), i32, i32,
+                                                  ctypes.POINTER(MatteResolveInputs), vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -856,6 +918,7 @@ class ParallelRenderer:
         self.last_history = None  # ... and each pixel's history length (n x H x W)
         self.last_variance = None  # variance=...: the variance pass's output (n x H x W, or H x W of render_denoised)
         self.last_clipped = None  # render_sequence(clip=...): 1 where the history was clipped (n x H x W)
+        self.last_resolved_linear = None  # matte=...: the edge-resolved image
 
     def set_tuning(self, tuning: Tuning):
         self._tuning = tuning
@@ -984,7 +1047,7 @@ class ParallelRenderer:
 
     def render_progressive(self, scene: Scene, width: int, height: int, pass_samples: int, time_budget=None,
                            until_changed_pixels=None, on_pass=None, adaptive=None, denoise=None, guide="first",
-                           specular=None) -> np.ndarray:
+                           specular=None, matte=None) -> np.ndarray:
         """Render the frame ``pass_samples`` samples at a time, on one device.
 
         ``self.settings.samples`` is the cap; the last pass is clipped to it.
@@ -1014,6 +1077,11 @@ class ParallelRenderer:
         ``last_linear`` and ``last_sample_counts`` stay those of the raw progression.
         ``guide`` ("first" or "specular", with ``specular`` the pass's parameters; §4.16) picks the feature
         pass as in ``render_denoised``.
+
+        ``matte`` (only with ``denoise``; True, a number of matte samples or a dict as in
+        ``render_denoised``): the matte is rendered once before the first pass, every pass's denoised image
+        goes through the edge resolve as the last step, ``on_pass`` receives and the call returns the
+        resolved image, and ``last_resolved_linear`` holds the last one's linear radiance.
         """
         t0 = time.perf_counter()
         if (len(self.devices) if self.devices else max(1, self.settings.num_devices)) > 1:
@@ -1026,6 +1094,9 @@ class ParallelRenderer:
         spec = _as_guide(guide, specular)
         if spec is not None and dn is None:
             raise RenderError('render_progressive: guide="specular" guides the denoiser and needs denoise')
+        mopt = _as_matte_option(matte, "render_progressive")
+        if mopt is not None and dn is None:
+            raise RenderError("render_progressive: matte resolves the denoised preview and needs denoise")
         import torch
 
         dev = self.devices[0] if self.devices else 0
@@ -1046,6 +1117,9 @@ class ParallelRenderer:
                 fst = Settings.from_buffer_copy(self.settings)
                 fst.samples = min(cap, int(pass_samples))
                 self._guide_pass(ctx, width, height, fst, feat, None, spec)
+                if mopt is not None:
+                    mt = self._matte_pass(ctx, width, height, fst, mopt,
+                                          feat["object"].data_ptr() if spec is None else None)
             ctx.progressive_begin(width, height, self.settings)
             if adaptive is not None:
                 ctx.progressive_set_adaptive(adaptive["tolerance"], adaptive.get("patience", 1),
@@ -1062,9 +1136,12 @@ class ParallelRenderer:
                         denoise_async(width, height, lin.data_ptr(), feat["normal"].data_ptr(),
                                       feat["depth"].data_ptr(), feat["albedo"].data_ptr(), feat["object"].data_ptr(),
                                       out_lin.data_ptr(), out_rgba.data_ptr(), work.data_ptr(), nbytes, dn, 0)
+                        if mopt is not None:
+                            self._matte_apply(width, height, mopt, mt, out_lin.data_ptr())
                     torch.cuda.synchronize()
                     done += n
-                    img = (out_rgba if dn is not None else cur).cpu().numpy().reshape(height, width, 4)
+                    shown = mt["rgba"] if mopt is not None else (out_rgba if dn is not None else cur)
+                    img = shown.cpu().numpy().reshape(height, width, 4)
                     changed = int(delta[0].item()) & 0xFFFFFFFF if k > 0 else None
                     if on_pass is not None:
                         on_pass(done, img, changed)
@@ -1087,6 +1164,8 @@ class ParallelRenderer:
             self.last_linear = lin.cpu().numpy().reshape(height, width, 3)
             if dn is not None:
                 self.last_denoised_linear = out_lin.cpu().numpy().reshape(height, width, 3)
+            if mopt is not None:
+                self.last_resolved_linear = mt["linear"].cpu().numpy().reshape(height, width, 3)
             self.last_sample_counts = counts.cpu().numpy().view(np.uint32).reshape(height, width)
         self.last_progressive_state = state
         self.last_samples = done
@@ -1106,7 +1185,7 @@ class ParallelRenderer:
 
     def render_sequence(self, scene: Scene, width: int, height: int, cameras, seeds=None, temporal=None,
                         denoise=None, variance=None, guide="first", specular=None, offsets=None, clip=None,
-                        light_offsets=None) -> np.ndarray:
+                        light_offsets=None, matte=None) -> np.ndarray:
         """The scene from each of ``cameras`` (Camera structs or scene-file camera dicts; any number):
         an (n, H, W, 4) uint8 array, frame f that of ``render`` with the scene's camera replaced by
         cameras[f] and seed seeds[f] (None: the renderer's seed), byte for byte.
@@ -1155,8 +1234,18 @@ class ParallelRenderer:
 
         light_offsets (an (n, num_lights, 3) array; §4.18): frame f is the scene with light i moved by
         light_offsets[f][i] (Scene.relit), rendered one by one as with ``offsets``, with which it composes.
-        Lights are not part of the motion table: a moving light is what ``clip`` is for."""
+        Lights are not part of the motion table: a moving light is what ``clip`` is for.
+
+        matte (True, a number of matte samples or a dict as in ``render_denoised``; §4.19; only together with
+        ``temporal``): each frame gets an object-level matte with its own camera, seed and scene, and the
+        frame that is SHOWN -- the filtered one with ``denoise`` or ``variance``, else the accumulated one --
+        goes through rt_matte_resolve_async as the last step.  The resolved frame is returned but never fed
+        back: the history stays the unfiltered accumulation.  ``last_resolved_linear`` is (n, H, W, 3)
+        float32.  With matte None nothing changes."""
         t0 = time.perf_counter()
+        mopt = _as_matte_option(matte, "render_sequence")
+        if mopt is not None and (temporal is None or temporal is False):
+            raise RenderError("render_sequence: matte resolves the accumulated frames and needs temporal")
         hc = None if clip is None or clip is False else _as_history_clip(clip)
         if hc is not None and (temporal is None or temporal is False):
             raise RenderError("render_sequence: clip rectifies the accumulated history and needs temporal")
@@ -1256,6 +1345,12 @@ class ParallelRenderer:
                 if spec is not None:  # the spatial filter's guide; the accumulation keeps the first hits
                     sg = {k: torch.zeros_like(v) for k, v in feat[0].items()}
                 fst = Settings.from_buffer_copy(self.settings)
+                if mopt is not None:  # one matte's buffers, reused frame by frame on the one stream
+                    mid, mcn = (torch.zeros(mopt[1] * npix, dtype=torch.int32, device="cuda") for _ in range(2))
+                    mre = torch.zeros(npix, dtype=torch.int32, device="cuda")
+                    rlin = torch.zeros((n, npix * 3), dtype=torch.float32, device="cuda")
+                    mst = Settings.from_buffer_copy(self.settings)
+                    mst.samples = mopt[0]
                 prev = None
                 if scenes is not None:
                     mot = [torch.from_numpy(t).to("cuda") for t in tables]
@@ -1318,7 +1413,17 @@ class ParallelRenderer:
                         denoise_async(width, height, acc[f].data_ptr(), gd["normal"].data_ptr(), gd["depth"].data_ptr(),
                                       gd["albedo"].data_ptr(), gd["object"].data_ptr(), dlin[f].data_ptr(),
                                       rgba[f].data_ptr(), work.data_ptr(), nbytes, dn, 0)
+                    if mopt is not None:  # the shown frame's last step; nothing of it is fed back
+                        mst.seed = fst.seed
+                        ctx.render_matte_async(width, height, mst,
+                                               MatteBuffers(mid.data_ptr(), mcn.data_ptr(), mre.data_ptr()),
+                                               params=default_matte(ranks=mopt[1]), camera=cams[f], stream=0)
+                        shown = dlin[f] if dn is not None or vg is not None else acc[f]
+                        matte_resolve_async(width, height, shown.data_ptr(), ft["object"].data_ptr(), mid.data_ptr(),
+                                            mcn.data_ptr(), mre.data_ptr(), mopt[1], mopt[0], rlin[f].data_ptr(),
+                                            rgba[f].data_ptr(), mopt[2], 0)
             torch.cuda.synchronize()
+            self.last_resolved_linear = rlin.cpu().numpy().reshape(n, height, width, 3) if mopt is not None else None
             self.last_linear = lin.cpu().numpy().reshape(n, height, width, 3)
             self.last_temporal_linear = acc.cpu().numpy().reshape(n, height, width, 3) if tp is not None else None
             self.last_history = cnt.cpu().numpy().reshape(n, height, width) if tp is not None else None
@@ -1388,6 +1493,86 @@ class ParallelRenderer:
             return {n: bufs[n].cpu().numpy().reshape((height, width, 3) if n in ("albedo", "normal")
                                                      else (height, width)) for n in names}
 
+    def render_matte(self, scene: Scene, width: int, height: int, samples: int = 16, ranks: int = 4,
+                     level="object", camera=None) -> dict:
+        """The matte layers of the frame (rt_context_render_matte_async) with ``samples``
+        camera rays per pixel and the renderer's seed and camera model, as numpy arrays: ``id`` and
+        ``count`` (K, H, W) int32 (K = ranks; -1 and 0 for an empty rank), ``rest`` (H, W) int32 and
+        ``coverage`` (K, H, W) float32 = count / samples.  level: "object" (the key is the object's index)
+        or "face" (object * 16 + the triangle's ordinal in its cube).  camera as in ``render_aov``.  Runs on
+        the renderer's first device."""
+        if int(width) < 1 or int(height) < 1:
+            raise RenderError(f"render_matte: invalid image size {width}x{height}")
+        if int(samples) < 1 or not 1 <= int(ranks) <= RT_MATTE_MAX_RANKS:
+            raise RenderError(f"render_matte: samples must be >= 1 and ranks in 1..{RT_MATTE_MAX_RANKS}")
+        if isinstance(camera, dict) and "position" not in camera:
+            raise RenderError("render_matte: a camera dict needs a position")
+        if camera is not None and not isinstance(camera, (dict, Camera, Scene)):
+            raise RenderError("render_matte: camera is a Camera, a Scene, a camera dict or None")
+        m = default_matte(ranks=int(ranks), level=level)
+        st = Settings.from_buffer_copy(self.settings)
+        st.samples = int(samples)
+        view = SceneView.from_buffer_copy(scene.view)
+        if camera is not None:
+            view.camera = _as_camera(camera)
+        _check(lib().rt_validate(ctypes.byref(view), width, height, ctypes.byref(st)))
+        import torch
+
+        dev = self.devices[0] if self.devices else 0
+        if self._prog_ctx is None:  # (the context render_progressive and render_aov use, kept)
+            self._prog_ctx = Context(dev)
+        ctx = self._prog_ctx
+        if self._tuning is not None:
+            ctx.set_tuning(self._tuning)
+        ctx.set_scene(scene)
+        npix, k = width * height, int(m.ranks)
+        with torch.cuda.device(dev):
+            ids = torch.zeros(max(k, 1) * npix, dtype=torch.int32, device="cuda")
+            cnt = torch.zeros(max(k, 1) * npix, dtype=torch.int32, device="cuda")
+            rest = torch.zeros(npix, dtype=torch.int32, device="cuda")
+            ctx.render_matte_async(width, height, st, MatteBuffers(ids.data_ptr(), cnt.data_ptr(), rest.data_ptr()),
+                                   params=m, camera=camera, stream=0)
+            torch.cuda.synchronize()
+            count = cnt.cpu().numpy().reshape(k, height, width)
+            return {"id": ids.cpu().numpy().reshape(k, height, width), "count": count,
+                    "rest": rest.cpu().numpy().reshape(height, width),
+                    "coverage": (count.astype(np.float64) / float(samples)).astype(np.float32)}
+
+    @staticmethod
+    def _matte_pass(ctx, width, height, settings, opt, d_object=None, camera=None):
+        """What the edge resolve of a ``matte=`` option reads beside the image, on the current
+        device: an object-level matte of the frame with opt's samples and ranks, and the frame's first-hit
+        ids (d_object; None: a first-hit pass with the frame's settings makes them).  A dict of tensors, its
+        own output buffers ``linear`` and ``rgba`` included."""
+        import torch
+
+        samples, ranks, _ = opt
+        npix = width * height
+        m = {n: torch.zeros((1 if n == "rest" else ranks) * npix, dtype=torch.int32, device="cuda")
+             for n in ("id", "count", "rest")}
+        if d_object is None:
+            m["object"] = torch.zeros(npix, dtype=torch.int32, device="cuda")
+            ctx.render_aov_async(width, height, settings, AovBuffers(None, None, None, None, m["object"].data_ptr()),
+                                 camera=camera, stream=0)
+            d_object = m["object"].data_ptr()
+        m["d_object"] = d_object
+        st = Settings.from_buffer_copy(settings)
+        st.samples = samples
+        ctx.render_matte_async(width, height, st,
+                               MatteBuffers(m["id"].data_ptr(), m["count"].data_ptr(), m["rest"].data_ptr()),
+                               params=default_matte(ranks=ranks), camera=camera, stream=0)
+        m["linear"] = torch.zeros(npix * 3, dtype=torch.float32, device="cuda")
+        m["rgba"] = torch.zeros(npix * 4, dtype=torch.uint8, device="cuda")
+        return m
+
+    @staticmethod
+    def _matte_apply(width, height, opt, m, d_color):
+        """rt_matte_resolve_async of the image at d_color with the buffers of ``_matte_pass``, into its
+        ``linear`` and ``rgba``."""
+        samples, ranks, rs = opt
+        matte_resolve_async(width, height, d_color, m["d_object"], m["id"].data_ptr(), m["count"].data_ptr(),
+                            m["rest"].data_ptr(), ranks, samples, m["linear"].data_ptr(), m["rgba"].data_ptr(), rs, 0)
+
     @staticmethod
     def _guide_pass(ctx, width, height, settings, feat, camera=None, spec=None):
         """The albedo, normal, depth and object a filter is guided by into the tensors of ``feat``: the
@@ -1416,7 +1601,7 @@ class ParallelRenderer:
         return feat, work, nbytes, out_lin, out_rgba
 
     def render_denoised(self, scene: Scene, width: int, height: int, params=None, camera=None,
-                        variance=None, guide="first", specular=None) -> np.ndarray:
+                        variance=None, guide="first", specular=None, matte=None) -> np.ndarray:
         """Render, then denoise: the frame of ``render`` (the renderer's settings; camera as
         in ``render_aov``), its first-hit feature buffers with the same samples, seed and camera model, and
         rt_denoise_async over both, on the renderer's first device.  params: a Denoise, a dict of its fields
@@ -1429,8 +1614,15 @@ class ParallelRenderer:
 
         guide ("first" or "specular"; §4.16): "specular" guides the filter by the specular-through albedo,
         normal, depth and object (``specular``: the pass's parameters as in ``render_aov``), so that it
-        stops at the edges of what a mirror shows; "first" is the first-hit guide."""
+        stops at the edges of what a mirror shows; "first" is the first-hit guide.
+
+        matte (True, a number of matte samples, or a dict with any of samples, ranks, radius, background;
+        §4.19): the filtered frame goes through the edge resolve as the last step -- an object-level matte of
+        the frame (16 samples, 4 ranks by default) and rt_matte_resolve_async -- and the resolved image is
+        returned; ``last_resolved_linear`` holds its linear radiance and ``last_denoised_linear`` stays the
+        filter's.  Without it nothing changes."""
         spec = _as_guide(guide, specular)
+        mopt = _as_matte_option(matte, "render_denoised")
         if int(width) < 1 or int(height) < 1:
             raise RenderError(f"render_denoised: invalid image size {width}x{height}")
         if int(self.settings.samples) < 1:
@@ -1479,10 +1671,17 @@ class ParallelRenderer:
                 denoise_async(width, height, lin.data_ptr(), feat["normal"].data_ptr(), feat["depth"].data_ptr(),
                               feat["albedo"].data_ptr(), feat["object"].data_ptr(), out_lin.data_ptr(),
                               out_rgba.data_ptr(), work.data_ptr(), nbytes, dn, 0)
+            if mopt is not None:  # (the first-hit ids: the guide's own unless it looked through the mirrors)
+                mt = self._matte_pass(ctx, width, height, self.settings, mopt,
+                                      feat["object"].data_ptr() if spec is None else None, camera)
+                self._matte_apply(width, height, mopt, mt, out_lin.data_ptr())
             torch.cuda.synchronize()
             self.last_variance = var.cpu().numpy().reshape(height, width) if vg is not None else None
             self.last_linear = lin.cpu().numpy().reshape(height, width, 3)
             self.last_denoised_linear = out_lin.cpu().numpy().reshape(height, width, 3)
+            if mopt is not None:
+                self.last_resolved_linear = mt["linear"].cpu().numpy().reshape(height, width, 3)
+                return mt["rgba"].cpu().numpy().reshape(height, width, 4)
             return out_rgba.cpu().numpy().reshape(height, width, 4)
 
     def rank_seconds(self) -> list:
@@ -1591,6 +1790,17 @@ class Context:
         cam = ctypes.byref(_as_camera(camera)) if camera is not None else None
         _check(lib().rt_context_render_aov_spec_async(self._h, width, height, ctypes.byref(settings), cam,
                                                        ctypes.byref(sp), ctypes.byref(out), ctypes.c_void_p(stream)))
+
+    def render_matte_async(self, width, height, settings: Settings, out: MatteBuffers, params=None, camera=None,
+                           stream: int = 0):
+        """rt_context_render_matte_async: the matte layers of the whole frame into the device
+        pointers of ``out`` (int32; d_id and d_count ``ranks`` planes of W*H, d_rest one); ``settings.samples``
+        is the number of matte samples.  params: a Matte, a dict of its fields or None (default_matte());
+        camera as in ``render_aov_async``.  No image is rendered and no state of the context changes."""
+        m = _as_one(params, Matte, default_matte, "matte")
+        cam = ctypes.byref(_as_camera(camera)) if camera is not None else None
+        _check(lib().rt_context_render_matte_async(self._h, width, height, ctypes.byref(settings), cam, ctypes.byref(m),
+                                                   ctypes.byref(out), ctypes.c_void_p(stream)))
 
     def progressive_begin(self, width, height, settings: Settings, rank: int = 0, world: int = 1,
                           layout: int = RT_LAYOUT_IMAGE):
@@ -2265,6 +2475,101 @@ def temporal_clip_host(cur: dict, prev=None, motion=None, params=None, moments: 
                                        ap["moments"] if moments else None, out.ctypes.data, cnt.ctypes.data,
                                        mom.ctypes.data if moments else None, clp.ctypes.data, rgba.ctypes.data))
     return (out, cnt, mom, clp, rgba) if moments else (out, cnt, clp, rgba)
+
+
+def default_matte(**over) -> Matte:
+    """rt_matte_default (ranks 4, level RT_MATTE_OBJECT; DESIGN.md §4.19), with the given fields replaced;
+    level may be "object" or "face"."""
+    m = Matte()
+    lib().rt_matte_default(ctypes.byref(m))
+    for k, v in over.items():
+        if k not in ("ranks", "level"):
+            raise RenderError(f"default_matte: no such field {k}")
+        if k == "level" and isinstance(v, str):
+            if v not in MATTE_LEVELS:
+                raise RenderError(f"default_matte: level is one of {sorted(MATTE_LEVELS)}")
+            v = MATTE_LEVELS[v]
+        setattr(m, k, v)
+    return m
+
+
+def default_matte_resolve(**over) -> MatteResolve:
+    """rt_matte_resolve_default (radius 2, background 0), with the given fields replaced."""
+    r = MatteResolve()
+    lib().rt_matte_resolve_default(ctypes.byref(r))
+    for k, v in over.items():
+        if k not in ("radius", "background"):
+            raise RenderError(f"default_matte_resolve: no such field {k}")
+        if k == "background":
+            v = (ctypes.c_double * 3)(*[float(c) for c in v])
+        setattr(r, k, v)
+    return r
+
+
+def matte_resolve_async(width: int, height: int, d_color: int, d_object: int, d_id: int, d_count: int, d_rest,
+                        ranks: int, samples: int, d_out_linear=None, d_out_rgba=None, params=None, stream: int = 0):
+    """rt_matte_resolve_async (DESIGN.md §4.19): every pointer a device pointer (an int; None: not given);
+    asynchronous on ``stream``.  d_id and d_count are ``ranks`` planes of an object-level matte of
+    ``samples`` samples, d_rest its rest plane or None; d_out_linear must not be d_color."""
+    p = _as_one(params, MatteResolve, default_matte_resolve, "matte resolve")
+    inp = MatteResolveInputs(d_color, d_object, d_id, d_count, d_rest, ranks, samples)
+    _check(lib().rt_matte_resolve_async(ctypes.byref(p), width, height, ctypes.byref(inp),
+                                        ctypes.c_void_p(d_out_linear), ctypes.c_void_p(d_out_rgba),
+                                        ctypes.c_void_p(stream)))
+
+
+def matte_resolve_host(color, object, id, count, rest=None, samples: int = 16, params=None):
+    """rt_matte_resolve_host: the edge resolve on numpy arrays, without a device.  color is (H, W, 3)
+    float32, object (H, W) int32, id and count (K, H, W) int32, rest (H, W) int32 or None.  Returns
+    (linear (H, W, 3) float32, rgba (H, W, 4) uint8)."""
+    what = "matte_resolve_host"
+    color = np.ascontiguousarray(color, np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise RenderError(f"{what}: color is an (H, W, 3) array")
+    h, w = color.shape[:2]
+    count = np.ascontiguousarray(count, np.int32)
+    if count.ndim != 3:
+        raise RenderError(f"{what}: count is a (K, H, W) array")
+    k = count.shape[0]
+    keep = []
+    a = _host_arrays(what, h, w, keep, object=(object, np.int32, (h, w)), id=(id, np.int32, (k, h, w)),
+                     count=(count, np.int32, (k, h, w)), rest=(rest, np.int32, (h, w)))
+    p = _as_one(params, MatteResolve, default_matte_resolve, "matte resolve")
+    inp = MatteResolveInputs(color.ctypes.data, a["object"], a["id"], a["count"], a["rest"], k, int(samples))
+    lin = np.zeros((h, w, 3), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    _check(lib().rt_matte_resolve_host(ctypes.byref(p), w, h, ctypes.byref(inp), lin.ctypes.data, rgba.ctypes.data))
+    return lin, rgba
+
+
+def matte_mask(matte: dict, key: int) -> np.ndarray:
+    """The (H, W) float32 coverage of one key in a matte of ``ParallelRenderer.render_matte``: the sum over
+    the ranks of ``coverage`` where ``id`` is the key (a key dropped from a pixel's ranks counts as 0 there)."""
+    ids, cov = np.asarray(matte["id"]), np.asarray(matte["coverage"], np.float32)
+    return np.where(ids == int(key), cov, np.float32(0)).sum(axis=0, dtype=np.float32)
+
+
+def _as_matte_option(matte, what):
+    """The (samples, ranks, MatteResolve) of a ``matte=`` option: True (16 samples, 4 ranks, the default
+    resolve), an int number of samples, or a dict with any of samples, ranks, radius, background."""
+    if matte is None or matte is False:
+        return None
+    opt = {}
+    if matte is True:
+        pass
+    elif isinstance(matte, int):
+        opt["samples"] = matte
+    elif isinstance(matte, dict):
+        opt = dict(matte)
+    else:
+        raise RenderError(f"{what}: matte is True, a number of samples or a dict")
+    for k in opt:
+        if k not in ("samples", "ranks", "radius", "background"):
+            raise RenderError(f"{what}: matte has no field {k}")
+    samples, ranks = int(opt.get("samples", 16)), int(opt.get("ranks", 4))
+    if samples < 1 or not 1 <= ranks <= RT_MATTE_MAX_RANKS:
+        raise RenderError(f"{what}: matte needs samples >= 1 and ranks in 1..{RT_MATTE_MAX_RANKS}")
+    return samples, ranks, default_matte_resolve(**{k: opt[k] for k in ("radius", "background") if k in opt})
 
 
 def variance_async(width: int, height: int, d_color: int, d_normal: int, d_depth: int, d_albedo=None, d_object=None,

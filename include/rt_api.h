@@ -665,6 +665,67 @@ int rt_context_render_aov_spec_async(rt_context* ctx, int32_t width, int32_t hei
                                      const rt_camera* camera /* NULL: the scene's */, const rt_aov_spec* spec,
                                      const rt_aov_spec_buffers* out, void* hip_stream);
 
+/* Matte layers: per pixel, WHICH objects its camera rays hit
+ * first and how many rays each -- what compositing calls a matte, and what
+ * rt_matte_resolve_async below rebuilds an antialiased silhouette from.
+ * rt_aov_buffers' d_object is only the id of the lowest hitting sample and
+ * d_coverage only the total; this is the list behind them.
+ *
+ * The definition.  Rays and hits are as rt_aov_buffers: sample s of pixel
+ * (x, y) is the render's own camera ray and its hit is hitWorld(ray, 0.001,
+ * +Inf).  n = settings->samples >= 1 is the number of MATTE samples; it is
+ * independent of a render's sample count, and since a ray depends on (seed,
+ * pixel, s) only, the first samples are the render's.
+ *   The key of a hitting sample.  level RT_MATTE_OBJECT: the hittable index,
+ *   the value d_object uses.  level RT_MATTE_FACE: object * 16 + f, where f is
+ *   0 for a sphere and for a cube the ordinal 0..11 of the hit triangle in
+ *   createCube's order (scene.go:150-190: faces -z, +x, +z, -x, +y, -y of a
+ *   positive size, two triangles each).  A miss has no key.
+ *   Slots.  A pixel has RT_MATTE_SLOTS (key, count) slots.  Samples are walked
+ *   in ascending s.  A hitting sample whose key is in a slot increments that
+ *   slot's count; otherwise, if a slot is free, it takes the next one with
+ *   count 1; otherwise `overflow` is incremented.  `hits` counts every hitting
+ *   sample.
+ *   Ranks.  The slots ordered by count descending, by key ascending among
+ *   equal counts.  K = params->ranks.
+ * Outputs, each a DEVICE pointer or NULL (not written), planar with plane r at
+ * r * W * H, so plane 0 is an image; pixel (x, y) at y * W + x like the image:
+ *   d_id     K planes of int32   the key of rank r, -1 for an empty rank
+ *   d_count  K planes of int32   its count, 0 for an empty rank
+ *   d_rest   one int32 plane     hits - (sum of the K counts): the dropped
+ *                                ranks and the overflow
+ * Counts are integers: sum(count) + rest == hits exactly, and hits equals
+ * d_coverage * n of the first-hit pass.
+ * The buffers depend on the scene, the size, the camera, the camera model,
+ * samples, seed, level and ranks only; force_bvh changes no bit of them.
+ *
+ * The call obeys rt_context_render_aov_async's rules: asynchronous on
+ * `hip_stream`, the WHOLE frame in image layout, camera NULL: the scene's (else
+ * copied before the call returns), no progression or work schedule disturbed, a
+ * render after the call byte for byte the render before it, nothing counted in
+ * rt_context_stats, its own HIP events for rt_context_last_kernel_seconds.
+ * RT_E_INVALID with a message, nothing enqueued and no buffer touched: what
+ * rt_context_render_aov_async refuses (with all THREE pointers NULL), a NULL
+ * params, ranks outside 1..RT_MATTE_MAX_RANKS, a level that is neither
+ * constant, and at the face level a scene of 2^27 or more objects. */
+#define RT_MATTE_SLOTS 16
+#define RT_MATTE_MAX_RANKS 8
+#define RT_MATTE_OBJECT 0
+#define RT_MATTE_FACE 1
+typedef struct {
+  int32_t ranks;  /* K, 1..RT_MATTE_MAX_RANKS */
+  int32_t level;  /* RT_MATTE_OBJECT or RT_MATTE_FACE */
+} rt_matte;
+typedef struct {
+  int32_t* d_id;     /* K * W*H */
+  int32_t* d_count;  /* K * W*H */
+  int32_t* d_rest;   /* W*H     */
+} rt_matte_buffers;
+void rt_matte_default(rt_matte* m); /* ranks 4, level RT_MATTE_OBJECT */
+int rt_context_render_matte_async(rt_context* ctx, int32_t width, int32_t height, const rt_settings* settings,
+                                  const rt_camera* camera /* NULL: the scene's */, const rt_matte* params,
+                                  const rt_matte_buffers* out, void* hip_stream);
+
 /* Progressive rendering: one frame's samples rendered over
  * several calls, with the image of the samples so far after each.  A context
  * holds at most one progression.  begin: the frame (size, rank, world and
@@ -1243,6 +1304,76 @@ int rt_temporal_clip_host(const rt_temporal* params, int32_t width, int32_t heig
                           const rt_temporal_frame* prev, const rt_motion* motion, const rt_history_clip* clip,
                           const float* cur_albedo, const float* prev_moments, float* out_color, float* out_count,
                           float* out_moments, float* out_clipped, uint8_t* out_rgba);
+
+/* The coverage-aware edge resolve: antialias the silhouettes
+ * of a low-sample image from an OBJECT-level matte.  Every filter above stops
+ * at object ids, so a 1-spp pixel on an object's edge stays one sample of one
+ * object, where the converged picture holds a blend of two.  Here a pixel that
+ * sees more than one object takes each object's share of its matte samples
+ * times that object's colour, gathered from the neighbours that belong to it.
+ * A pixel that sees one object is not changed at all.  Context-free like
+ * rt_denoise_async.
+ *
+ * Inputs, image layout, pixel (x, y) at p = y * W + x:
+ *   color   float3, required   any linear image of the frame: raw, denoised or accumulated
+ *   object  int32, required    the frame's d_object: whose colour color[q] is
+ *   id, count  K planes of int32 each, required: d_id and d_count of an
+ *              RT_MATTE_OBJECT matte of the frame with K ranks
+ *   rest    int32, optional    its d_rest; NULL counts as 0 everywhere
+ *   samples n >= 1             the matte's sample count
+ * Parameters (rt_matte_resolve; rt_matte_resolve_default):
+ *   radius      R in 1..4, default 2: the gather window is (2R + 1)^2
+ *   background  finite, default 0: the colour behind everything
+ *
+ * The arithmetic is binary64 `+ - * /` and comparisons only, floats widened
+ * before use and rounded once on store.  Per pixel p:
+ *   1. The parts, in this order: the ranks r = 0..K-1 with count_r[p] > 0, key
+ *      id_r[p]; the miss part with count = n - sum(those count_r) - rest[p]
+ *      and key -1, if that count is positive; the rest part with count
+ *      rest[p], if rest[p] > 0.  With fewer than two parts out = color[p] bit
+ *      for bit.
+ *   2. A rank or miss part's colour: sw = 0, sc[3] = 0; dy = -R..R outer,
+ *      dx = -R..R inner, q = (x + dx, y + dy); a tap is skipped when q is
+ *      outside the image or object[q] != key; otherwise
+ *      w = 1 / (1 + (dx * dx + dy * dy)), sw += w, sc[k] += w * color[q][k].
+ *      The colour is sc[k] / sw when sw > 0, else background[k] for the miss
+ *      part and color[p][k] for a rank.  The rest part's colour is color[p].
+ *   3. acc[3] = 0; in part order acc[k] += ((double)count / (double)n) *
+ *      part[k]; out[k] = (float)acc[k].
+ * out_rgba, if given, is rt_tonemap_rgba of the stored out.
+ *   - Every address comes from x, y, dx, dy and r: no input value can cause a
+ *     fault.  Counts whose sum exceeds n carry no contract on their values.
+ *   - Shares are geometric: a shadow's edge or a reflection's edge is not a
+ *     part and is untouched.  An object whose only visible pixels are mixed
+ *     has no neighbour to gather from and keeps the pixel's own colour.
+ *
+ * rt_matte_resolve_async: device pointers, no workspace, no context, no
+ * allocation; asynchronous on `hip_stream`.  RT_E_INVALID with a message,
+ * nothing enqueued and no buffer touched: a NULL params, color, object, id or
+ * count; both outputs NULL; out_linear == color (taps read neighbours); a size
+ * that rt_validate refuses; ranks outside 1..RT_MATTE_MAX_RANKS; samples < 1;
+ * radius outside 1..4; a background that is not finite.
+ * rt_matte_resolve_host does the same with host pointers and no device. */
+typedef struct {
+  int32_t radius;
+  int32_t _pad;
+  double background[3];
+} rt_matte_resolve;
+typedef struct {
+  const float* color;     /* W*H*3 */
+  const int32_t* object;  /* W*H   */
+  const int32_t* id;      /* ranks * W*H */
+  const int32_t* count;   /* ranks * W*H */
+  const int32_t* rest;    /* W*H, or NULL */
+  int32_t ranks;          /* K */
+  int32_t samples;        /* n */
+} rt_matte_resolve_inputs;
+void rt_matte_resolve_default(rt_matte_resolve* r); /* radius 2, background 0 */
+int rt_matte_resolve_async(const rt_matte_resolve* params, int32_t width, int32_t height,
+                           const rt_matte_resolve_inputs* in, float* d_out_linear /* may be NULL */,
+                           uint8_t* d_out_rgba /* may be NULL */, void* hip_stream);
+int rt_matte_resolve_host(const rt_matte_resolve* params, int32_t width, int32_t height,
+                          const rt_matte_resolve_inputs* in, float* out_linear, uint8_t* out_rgba);
 
 /* What a context has done so far (diagnostics): work schedules built (a new
  * scene, frame, rank or settings key; a measured re-cut counts too),
